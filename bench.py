@@ -7,9 +7,15 @@ standard-config proofs resident in HBM (BASELINE.json configs[1], "C2"), in the 
 tiled layout (P2V_FLAG_INPUT_TILED; --layout proof-major for the row-per-proof form).  By
 default two batches are in flight per GPU (two verifier workspaces on two streams, the
 async NO_SYNC path of the C ABI), so one batch's latency-bound transcript overlaps the
-other's Merkle work; the one-at-a-time figure is reported alongside ("serial").  N GPUs =
-N ranks (torchrun), each verifying its own batch (proofs shard with no data-path
-collective: weak scaling); value = all proofs of all ranks / max-over-ranks time.
+other's Merkle work.  N GPUs = N ranks (torchrun), each verifying its own batch (proofs shard
+with no data-path collective: weak scaling); value = all proofs of all ranks / max-over-ranks time.
+
+A plain run does what that figure needs and no more: it generates the workload, warms up, times
+--steps steps and prints the line.  --full adds everything else the benchmark measures, each in
+runs of its own after the headline pass: the one-at-a-time pass ("serial") with its per-kernel
+times and the roofline built on them, the C5 and C3 legs, the drop-in, ingest and from-host legs
+and the CPU baseline (--quick / --no-c5 / --no-c3 / --no-host-legs / --no-cpu-baseline trim it).
+--dump-outputs DIR writes the statuses the last timed step returned (DIR/status.npy).
 
 Workload: synthetic valid proofs from the build's prover (csrc/gen): standard recursion
 config (degree_bits 12, rate_bits 3, cap_height 4, 28 queries, arity 16, PoW 16, 135 wires /
@@ -705,6 +711,59 @@ def c3_leg(p2v, args, threads, dev, local, streams):
     return out
 
 
+def hbm_roofline(kavg, info, B, pmc_workload):
+    """The line's `roofline` object, from the serial pass's per-kernel times (kavg).  bound: the
+    binding resource is the integer VALU issue rate (valu.issue, from the PMC pass); achieved /
+    peak / frac stay the HBM form the metric asks for.  pmc_workload: this
+    run's workload is the PMC pass's own, so its per-kernel traffic table applies."""
+    kb = kernel_bytes_model(info, info.trace_words)
+    # dominant kernel: the longest launch on the main stream (k_transcript / k_vanish / k_fri /
+    # k_lut run on the side stream under k_leaf / k_merkle and do not set the step time)
+    main_stream = [k for k in ("k_transpose", "k_phase1", "k_leaf", "k_merkle", "k_status") if k in kavg]
+    dom = max(main_stream, key=kavg.get)
+    achieved = kb[dom] * B / (kavg[dom] * 1e-3) / 1e9
+    # HBM bytes per launch of the dominant kernel from the committed rocprofv3 PMC passes
+    # (profiles/<tag>_pmc_traffic.json, with the counter correction tools/pmc_summary.py applies;
+    # the same tag as valu.issue), as GB/s over this run's measured launch time; null if no PMC summary.
+    traffic, traffic_bytes, ktable = None, None, None
+    tag = pmc_tag()
+    pmc = os.path.join(ROOT, "profiles", f"{tag}_pmc_traffic.json") if tag else ""
+    if tag:
+        try:
+            pt = json.load(open(pmc))
+            if pmc_workload:
+                ktable = kernel_traffic_table(pt, info, B)   # the PMC pass's own workload only
+            traffic_bytes = sum(v for k, v in pt.items() if not k.startswith("_") and slot_of(k) == dom and isinstance(v, (int, float))) or None
+            if traffic_bytes:
+                traffic_bytes = int(traffic_bytes * B / 4096)   # the PMC passes ran 4096-proof batches
+                traffic = round(traffic_bytes / (kavg[dom] * 1e-3) / 1e9, 2)
+        except Exception:
+            traffic = None
+    return {"bound": "valu", "kernel": dom, "achieved": round(achieved, 2), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+            "frac": round(achieved / HBM_PEAK_GBPS, 6), "traffic": traffic,
+            "traffic_bytes_per_launch": traffic_bytes, "algorithmic_bytes_per_launch": kb[dom] * B,
+            "traffic_source": os.path.relpath(pmc, ROOT) if pmc else None,
+            "kernels": ktable,
+            "valu_issue_frac": None,
+            "note": "binding resource: integer VALU issue (Poseidon), valu_issue_frac = valu.issue.step_frac; "
+                    "achieved/peak/frac: the dominant kernel's algorithmic HBM bytes over its launch time"}
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, rank, statuses):
+    """--dump-outputs: what the last timed step handed back to its caller, the int8 status of every
+    proof of its batch (1 accepted, 0 / negative: the check that failed), as float32 in
+    DIR/status.npy (rank 0; DIR/status_rank<r>.npy for the other ranks, whose batches differ).
+    The workload is generated from fixed seeds, so two builds given the same arguments verify the
+    same proofs and their files compare element for element."""
+    out = np.ascontiguousarray(statuses, dtype=np.float32)
+    assert out.nbytes <= DUMP_MAX_BYTES, f"{out.nbytes} bytes of statuses: more than a batch in HBM can hold"
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "status.npy" if rank == 0 else f"status_rank{rank}.npy"), out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=None,
@@ -739,12 +798,21 @@ def main():
     ap.add_argument("--dist-backend", default="gloo",
                     help="the default process group: gloo (the bench's cross-rank operations are CPU-side barriers and "
                          "reductions; no data-path collective) or nccl (= RCCL, with a gloo side group for those operations)")
-    ap.add_argument("--quick", action="store_true", help="device-resident figure only (no ingest / PCIe / CPU / C5 legs)")
-    ap.add_argument("--no-c5", action="store_true", help="skip the C5 leg (1M proofs sharded over the ranks)")
-    ap.add_argument("--no-c3", action="store_true", help="skip the C3 leg (65536 lookup-circuit proofs, one GPU)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline pass, also run everything else the benchmark measures: the one-at-a-time (serial) pass "
+                         "with its per-kernel times and roofline figures, the C5 and C3 legs, the drop-in, ingest and from-host legs "
+                         "and the CPU baseline.  Without it the run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to its caller (the per-proof statuses of "
+                         "its batch) as DIR/status.npy, float32; ranks above 0 write DIR/status_rank<r>.npy")
+    ap.add_argument("--quick", action="store_true", help="with --full: the serial pass only (no ingest / PCIe / CPU / C5 legs)")
+    ap.add_argument("--no-c5", action="store_true", help="with --full: skip the C5 leg (1M proofs sharded over the ranks)")
+    ap.add_argument("--no-c3", action="store_true", help="with --full: skip the C3 leg (65536 lookup-circuit proofs, one GPU)")
     ap.add_argument("--no-host-legs", action="store_true",
-                    help="skip the drop-in, ingest, from-host and CPU-baseline legs (device-resident C2 / C5 / C3 only)")
+                    help="with --full: skip the drop-in, ingest, from-host and CPU-baseline legs (device-resident C2 / C5 / C3 only)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and args.gpus and args.gpus > 1:
@@ -902,21 +970,29 @@ def main():
     for i in range(args.warmup):
         bvs[i % nv].run_device(d_proofs.data_ptr(), B, d_res[i % nv].data_ptr(), stream=streams[i % nv].cuda_stream, sync=False,
                                tiled=lay_tiled, lookahead=bool(args.lookahead))
+    # the headline pass: pipelined over the nv workspaces, or (--inflight 1) one batch at a time
+    dt_serial, ktimes, clock_serial, check_serial = None, {}, None, None
     if nv > 1:
         dt, _, clock, own, check = timed(args.steps, True)
         ok = all(bool((r == d_expect).all()) for r in d_res[:min(nv, args.steps)])
+        last = d_res[(args.steps - 1) % nv]
+    else:
+        dt, ktimes, clock, own, check = timed(args.steps, False)
+        dt_serial, clock_serial, check_serial = dt, clock, check
+        ok = bool((d_res[0] == d_expect).all())
+        last = d_res[0]
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, last.cpu().numpy())
+    if nv > 1 and args.full:
         for r in d_res:
             r.zero_()
-    # serial pass: per-kernel durations (HIP events recorded on the run's streams inside libp2v)
-    dt_serial, ktimes, clock_serial, own_serial, check_serial = timed(args.steps, False)
-    if nv > 1:
+        # serial pass: per-kernel durations (HIP events recorded on the run's streams inside libp2v)
+        dt_serial, ktimes, clock_serial, _, check_serial = timed(args.steps, False)
         ok = ok and bool((d_res[0] == d_expect).all())
-    else:
-        dt, clock, own, check = dt_serial, clock_serial, own_serial, check_serial
-        ok = bool((d_res[0] == d_expect).all())
-    # every timed step of both passes checked on the device, on every rank
+    # every timed step of every pass checked on the device, on every rank
     ok = ok and check["mismatches"] == 0 and check["steps"] == args.steps
-    ok = ok and check_serial["mismatches"] == 0 and check_serial["steps"] == args.steps
+    if check_serial is not None:
+        ok = ok and check_serial["mismatches"] == 0 and check_serial["steps"] == args.steps
     ok = all(v > 0 for v in gather_over_ranks(1.0 if ok else 0.0, world, cpu_grp))
     verified_steps = int(min(gather_over_ranks(float(check["steps"] if check["mismatches"] == 0 else 0), world, cpu_grp)))
     run_clock = (clock.get("run_clock") or {}).get("clock_ghz")
@@ -925,36 +1001,14 @@ def main():
     value = total / dt
     kavg = {k: float(np.mean(v)) for k, v in ktimes.items()}
     c5 = None
-    if not args.quick and not args.no_c5:
+    legs = args.full and not args.quick   # the legs beside the C2 figure run under --full only
+    if legs and not args.no_c5:
         c5 = c5_leg(p2v, vk, info, d_proofs, d_expect, B, world, local, dev, cpu_grp, streams, lay_tiled,
                     stagger=args.stagger)
     c3 = None
-    if world == 1 and not args.quick and not args.no_c3 and not args.lookups and real:
+    if world == 1 and legs and not args.no_c3 and not args.lookups and real:
         c3 = c3_leg(p2v, args, threads, dev, local, streams)
     if rank == 0:
-        kb = kernel_bytes_model(info, info.trace_words)
-        # dominant kernel: the longest launch on the main stream (k_transcript / k_vanish / k_fri /
-        # k_lut run on the side stream under k_leaf / k_merkle and do not set the step time)
-        main_stream = [k for k in ("k_transpose", "k_phase1", "k_leaf", "k_merkle", "k_status") if k in kavg]
-        dom = max(main_stream, key=kavg.get)
-        achieved = kb[dom] * B / (kavg[dom] * 1e-3) / 1e9
-        # HBM bytes per launch of the dominant kernel from the committed rocprofv3 PMC passes
-        # (profiles/<tag>_pmc_traffic.json, corrected per MI355X_MICROARCH.md §HBM; the same tag
-        # as valu.issue), as GB/s over this run's measured launch time; null if no PMC summary.
-        traffic, traffic_bytes, ktable = None, None, None
-        tag = pmc_tag()
-        pmc = os.path.join(ROOT, "profiles", f"{tag}_pmc_traffic.json") if tag else ""
-        if tag:
-            try:
-                pt = json.load(open(pmc))
-                if real and info.degree_bits == 12 and not args.lookups and not args.ext and not arities:
-                    ktable = kernel_traffic_table(pt, info, B)   # the PMC pass's own workload only
-                traffic_bytes = sum(v for k, v in pt.items() if not k.startswith("_") and slot_of(k) == dom and isinstance(v, (int, float))) or None
-                if traffic_bytes:
-                    traffic_bytes = int(traffic_bytes * B / 4096)   # the PMC passes ran 4096-proof batches
-                    traffic = round(traffic_bytes / (kavg[dom] * 1e-3) / 1e9, 2)
-            except Exception:
-                traffic = None
         ppp = perms_per_proof(info) + 114 + 1
         out = {
             "metric": METRIC, "value": round(value, 1), "unit": "proofs/s", "n_gpus": world, "steps": args.steps,
@@ -973,47 +1027,41 @@ def main():
                        **({"hw_queues": args.hw_queues} if args.hw_queues else {})},
             "clock": {**clock, "note": "the timed pass on the device clock: HIP events on each workspace stream (start before its "
                                        "first launch, one after every launch); step_ms = intervals between successive completions"},
-            "serial": {"value": round(total / dt_serial, 1), "ms_per_step": round(dt_serial / args.steps * 1e3, 4),
-                       "clock": clock_serial,
-                       "note": "one batch at a time, host-synchronised per step; kernel_ms and roofline come from this pass"},
-            # bound: the binding resource is the integer VALU issue rate (valu.issue, from the PMC
-            # pass); achieved / peak / frac stay the HBM form the metric asks for
-            "roofline": {"bound": "valu", "kernel": dom, "achieved": round(achieved, 2), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBPS, 6), "traffic": traffic,
-                         "traffic_bytes_per_launch": traffic_bytes, "algorithmic_bytes_per_launch": kb[dom] * B,
-                         "traffic_source": os.path.relpath(pmc, ROOT) if pmc else None,
-                         "kernels": ktable,
-                         "valu_issue_frac": None,
-                         "note": "binding resource: integer VALU issue (Poseidon), valu_issue_frac = valu.issue.step_frac; "
-                                 "achieved/peak/frac: the dominant kernel's algorithmic HBM bytes over its launch time"},
+            # the one-at-a-time pass and what derives from its per-kernel times (--full, or --inflight 1
+            # where it is the headline pass itself)
+            **({"serial": {"value": round(total / dt_serial, 1), "ms_per_step": round(dt_serial / args.steps * 1e3, 4),
+                           "clock": clock_serial,
+                           "note": "one batch at a time, host-synchronised per step; kernel_ms and roofline come from this pass"},
+                "roofline": hbm_roofline(kavg, info, B, real and info.degree_bits == 12 and not args.lookups and not args.ext and not arities)}
+               if kavg else {}),
             "valu": {"perms_per_proof": ppp, "perm_rate_G": round(value / world * ppp / 1e9, 3),
                      "perms_note": "perms_per_proof counts every query path in full (the reference's work); the shared-node "
                                    "Merkle kernels hash each node several queries share once, ~86.6 % of the compressions "
                                    "(DESIGN.md 5.6), so perm_rate_G is reference-equivalent permutations/s",
                      "issue": valu_roofline(kavg, dt / args.steps * 1e3, B, run_clock)
                      if (real and info.degree_bits == 12 and not args.lookups and not args.ext and not arities) else None},   # the PMC pass's own workload only
-            "kernel_ms": {k: round(v, 4) for k, v in kavg.items()},
+            **({"kernel_ms": {k: round(v, 4) for k, v in kavg.items()}} if kavg else {}),
             "verified_all": ok,
             "verified_steps": verified_steps,
-            "verification": {"pipelined": check, "serial": check_serial,
+            "verification": {"pipelined": check, **({"serial": check_serial} if check_serial is not None else {}),
                              "note": "every timed step's statuses compared with the expected vector on the device, on the "
                                      "launch's stream right after it (p2v_count_mismatches); steps = checks that ran, min over ranks"},
             "per_rank": per_rank,
             "build": {**build, "host_threads_per_rank": threads, "local_world": local_world},
         }
-        if out["valu"]["issue"]:
+        if out["valu"]["issue"] and "roofline" in out:
             out["roofline"]["valu_issue_frac"] = out["valu"]["issue"]["step_frac"]
         if c5 is not None:
             out["c5"] = c5
         if c3 is not None:
             out["c3"] = c3
-        if world == 1 and not args.quick and not args.no_host_legs:
+        if world == 1 and legs and not args.no_host_legs:
             out["dropin"] = dropin_leg(p2v, gc, proofs, rows, expect, local)
             out["ingest"] = ingest_rate(vk, proofs, threads)
             out["h2d_end_to_end"] = h2d_rate(bvs, rows, B, expect, local=local)
             out["json_end_to_end"] = json_rate(bvs, proofs, B)
             out["bytes_end_to_end"] = bytes_rate(bvs, proofs, B, local=local)
-        if world == 1 and not args.no_cpu_baseline and not args.quick and not args.no_host_legs:
+        if world == 1 and legs and not args.no_cpu_baseline and not args.no_host_legs:
             out["cpu_baseline"] = cpu_baseline(gc, proofs, threads)
         print(json.dumps(out), flush=True)
     if world > 1:

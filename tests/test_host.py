@@ -254,6 +254,26 @@ def test_bench_refuses_mislabelled_gpu_count():
     assert r.returncode == 2 and "refusing" in r.stderr
 
 
+def test_bench_dump_outputs_and_full_option(tmp_path):
+    """bench.py --dump-outputs writes the last timed step's int8 statuses as float32 .npy files
+    (rank 0: status.npy), values unchanged; --full and --dump-outputs are options of the parser and
+    a plain run asks for neither."""
+    import subprocess
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import bench
+    st = np.array([1, -1, 1, -2, 0, -3, 1], dtype=np.int8)
+    d = tmp_path / "out" / "nested"
+    bench.dump_outputs(str(d), 0, st)
+    bench.dump_outputs(str(d), 3, st[::-1])
+    a, b = np.load(d / "status.npy"), np.load(d / "status_rank3.npy")
+    assert a.dtype == np.float32 and b.dtype == np.float32
+    assert np.array_equal(a, st.astype(np.float32)) and np.array_equal(b, st[::-1].astype(np.float32))
+    assert sorted(os.listdir(d)) == ["status.npy", "status_rank3.npy"]
+    h = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
+    assert h.returncode == 0 and "--full" in h.stdout and "--dump-outputs DIR" in h.stdout
+
+
 def test_host_readers_under_asan_and_ubsan(tmp_path):
     """tools/asan/run.sh: every host reader (JSON circuit / proof, template packer, words, bytes)
     built with -fsanitize=address,undefined and fed seeded mutations of real inputs; any memory

@@ -52,9 +52,11 @@ def test_field_inverse_semantics():
     ("MulExtensionGate { num_ops: 13 }", 8),
     ("NoopGate", 9),
     ("PublicInputGate", 10),
-    ("PoseidonGate(PhantomData<plonky2_field::goldilocks_field::GoldilocksField>)<WIDTH=12>", 11),
-    ("PoseidonMdsGate(PhantomData<plonky2_field::goldilocks_field::GoldilocksField>)<WIDTH=12>", 12),
-    ("RandomAccessGate { bits: 4, num_copies: 4, num_extra_constants: 2, _phantom: PhantomData<plonky2_field::goldilocks_field::GoldilocksField> }<D=2>", 13),
+    # explicit ids: the Rust paths in these names hold "::", pytest's own node-id separator
+    pytest.param("PoseidonGate(PhantomData<plonky2_field::goldilocks_field::GoldilocksField>)<WIDTH=12>", 11, id="PoseidonGate-11"),
+    pytest.param("PoseidonMdsGate(PhantomData<plonky2_field::goldilocks_field::GoldilocksField>)<WIDTH=12>", 12, id="PoseidonMdsGate-12"),
+    pytest.param("RandomAccessGate { bits: 4, num_copies: 4, num_extra_constants: 2, _phantom: PhantomData<plonky2_field::goldilocks_field::GoldilocksField> }<D=2>", 13,
+                 id="RandomAccessGate-13"),
     ("ReducingGate { num_coeffs: 43 }", 14),
     ("ReducingExtensionGate { num_coeffs: 32 }", 15),
     ("SomethingElse", 16),

@@ -12,7 +12,7 @@ cd /tmp && export TMPDIR=/tmp
 cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/prof_$TAG
 mkdir -p $OUT
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -T --output-format csv -d $OUT/trace -o run -- python3 bench.py --steps 10 --warmup 2 --quick > $OUT/bench_under_trace.json 2> $OUT/trace.err
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -T --output-format csv -d $OUT/trace -o run -- python3 bench.py --steps 10 --warmup 2 --full --quick > $OUT/bench_under_trace.json 2> $OUT/trace.err
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -T --output-format csv -d $OUT/trace_serial -o run -- python3 bench.py --steps 10 --warmup 2 --quick --inflight 1 > $OUT/bench_under_trace_serial.json 2> $OUT/trace_serial.err
 timeout -s KILL 150 rocprofv3 --pmc FETCH_SIZE -T --output-format csv -d $OUT/pmc_fetch -o run -- python3 bench.py --steps 3 --warmup 1 --quick --inflight 1 > /dev/null 2> $OUT/pmc_fetch.err
 timeout -s KILL 150 rocprofv3 --pmc WRITE_SIZE -T --output-format csv -d $OUT/pmc_write -o run -- python3 bench.py --steps 3 --warmup 1 --quick --inflight 1 > /dev/null 2> $OUT/pmc_write.err
