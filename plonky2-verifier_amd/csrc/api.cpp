@@ -14,13 +14,9 @@
 #include "../../include/p2v.h"
 #include "circuit.hpp"
 #include "dev.h"
-#ifndef P2V_PROOF_MAJOR
-#define P2V_PROOF_MAJOR 1   // see devcommon.h ld()
-#endif
 #include "gl.h"
 #include "poseidon_constants.h"
 
-extern "C" __global__ void k_transpose(const uint64_t*, int64_t, int, uint64_t*, int);
 extern "C" __global__ void k_phase1(DevCircuit, int, int);
 extern "C" __global__ void k_phase1_lane(DevCircuit, int, int);
 extern "C" __global__ void k_phase1_pair(DevCircuit, int, int);
@@ -34,12 +30,6 @@ extern "C" __global__ void k_merkle_row(DevCircuit);
 extern "C" __global__ void k_merkle_plan(DevCircuit);
 extern "C" __global__ void k_merkle_cse(DevCircuit);
 extern "C" __global__ void k_merkle_fix(DevCircuit);
-#ifndef P2V_PLAN_WAVES
-#define P2V_PLAN_WAVES 16   // as kernels.hip
-#endif
-#ifndef P2V_FIX_BLOCKS
-#define P2V_FIX_BLOCKS 256   // k_merkle_fix grid: its blocks wait for free slots beside the other batch's kernels
-#endif
 extern "C" __global__ void k_merkle_resolve(DevCircuit);
 extern "C" __global__ void k_fri(DevCircuit);
 extern "C" __global__ void k_vanish_r2(DevCircuit);
@@ -68,7 +58,9 @@ thread_local std::string g_err;
 int fail(int code, const std::string& msg) { g_err = msg; return code; }
 
 // per-kernel timing slots; k_fri and k_vanish run on the side stream, concurrently with k_merkle
-// (k_leaf + k_transcript: the split form of k_phase1, env P2V_PHASE1=split, measurement only)
+// (k_leaf + k_transcript: the split form of k_phase1, env P2V_PHASE1=split, measurement only).
+// Slot 0 is the retired transposing build's; it keeps its name and place (callers index by this
+// list) and is never recorded.
 const char* kKernelNames = "k_transpose,k_phase1,k_merkle,k_fri,k_vanish,k_status,k_vanish_final,k_lut,k_leaf,k_transcript";
 constexpr int kNumKernels = 10;
 
@@ -140,7 +132,7 @@ struct p2v_verifier {
   std::vector<DevBuf> bufs;
   size_t in_bytes = 0;              // the host-input staging buffer `in`, allocated by the first run that needs it
                                     // (device-resident batches never do: a 131 072-proof workspace saves 16.6 GB)
-  DevBuf in, soa, chal, leafdig, mk, fbits, qvals, van, vparts, lutre, lutpart, res, trace;
+  DevBuf in, chal, leafdig, mk, fbits, qvals, van, vparts, lutre, lutpart, res, trace;
   DevBuf m_plan, m_fol, m_chain, m_count, m_fix, m_badq, m_node;   // shared-node Merkle paths (dev.h mcse)
   DevBuf t_cs, t_kis, t_gkind, t_gpar, t_ggrp, t_gwoff, t_w, t_gs, t_ge, t_lin, t_lout, t_loff, t_llen, t_tw, t_ops, t_vit, t_rin, t_rout, t_roff, t_rch, t_pbase, t_pw;
   hipEvent_t ev[2 * kNumKernels];   // start/end per kernel
@@ -442,7 +434,7 @@ void p2v_verifier_free(p2v_verifier* v) {
     }
   }
   (void)hipSetDevice(v->device);
-  for (DevBuf* b : {&v->in, &v->soa, &v->chal, &v->leafdig, &v->mk, &v->fbits, &v->qvals, &v->van, &v->vparts, &v->lutre, &v->res, &v->trace, &v->t_cs, &v->t_kis,
+  for (DevBuf* b : {&v->in, &v->chal, &v->leafdig, &v->mk, &v->fbits, &v->qvals, &v->van, &v->vparts, &v->lutre, &v->res, &v->trace, &v->t_cs, &v->t_kis,
                     &v->t_gkind, &v->t_gpar, &v->t_ggrp, &v->t_gwoff, &v->t_w, &v->t_gs, &v->t_ge, &v->t_lin, &v->t_lout, &v->t_loff, &v->t_llen, &v->t_tw, &v->t_ops, &v->t_vit, &v->t_rin, &v->t_rout, &v->t_roff, &v->t_rch, &v->t_pbase, &v->t_pw, &v->lutpart, &v->chal2, &v->j_blob, &v->j_offs, &v->j_skel, &v->j_tok, &v->j_ok,
                     &v->b_rsrc, &v->b_rdst, &v->b_rlen, &v->b_coff, &v->b_cval,
                     &v->m_plan, &v->m_fol, &v->m_chain, &v->m_count, &v->m_fix, &v->m_badq, &v->m_node})
@@ -637,7 +629,6 @@ int p2v_verifier_create(const p2v_circuit* pc, int device, size_t max_batch, p2v
   const size_t B = v->Bmax;
   const size_t chw = (size_t)(4 + 7 * d.r + 4 + 2 * d.S + 1 + d.Q + 4);
   v->in_bytes = (size_t)L.words * v->Bmax * 8;   // whole 64-proof tiles (P2V_FLAG_INPUT_TILED); allocated on first use
-  if (e == hipSuccess && !P2V_PROOF_MAJOR) e = v->soa.alloc((size_t)L.words * B * 8);   // the transposed batch
   if (e == hipSuccess) e = v->chal.alloc(chw * B * 8);
   if (e == hipSuccess) e = v->chal2.alloc(chw * B * 8);
   if (e == hipSuccess) e = v->leafdig.alloc((size_t)d.Q * d.T * 4 * B * 8);
@@ -700,7 +691,7 @@ int p2v_verifier_create(const p2v_circuit* pc, int device, size_t max_batch, p2v
   d.lut_rin = (const uint32_t*)v->t_rin.p; d.lut_rout = (const uint32_t*)v->t_rout.p; d.lut_roff = (const int64_t*)v->t_roff.p; d.lut_rchunks = (const int32_t*)v->t_rch.p; d.lut_pbase = (const int32_t*)v->t_pbase.p;
   d.twiddles = (const uint64_t*)v->t_tw.p; d.tops = (const int32_t*)v->t_ops.p; d.vitems = (const int32_t*)v->t_vit.p;
   d.pos_w = (const uint64_t*)v->t_pw.p;
-  d.soa = (const uint64_t*)v->soa.p; d.chal = (uint64_t*)v->chal.p; d.leafdig = (uint64_t*)v->leafdig.p; d.mk_ok = (uint8_t*)v->mk.p;
+  d.chal = (uint64_t*)v->chal.p; d.leafdig = (uint64_t*)v->leafdig.p; d.mk_ok = (uint8_t*)v->mk.p;
   d.fri_bits = (uint32_t*)v->fbits.p; d.qvals = (uint64_t*)v->qvals.p; d.van = (uint64_t*)v->van.p; d.vparts = (uint64_t*)v->vparts.p; d.lutre = (uint64_t*)v->lutre.p; d.lutpart = (uint64_t*)v->lutpart.p;
   *out = v;
   return P2V_OK;
@@ -733,10 +724,6 @@ int p2v_verifier_run(p2v_verifier* v, const uint64_t* proofs, size_t n, int8_t* 
   d.unit_filters = (flags & P2V_FLAG_UNIT_FILTERS) ? 1 : 0;
   d.tiled = (flags & P2V_FLAG_INPUT_TILED) ? 1 : 0;
   d.wstride = d.tiled ? 64 : 1;
-  if (d.tiled && !P2V_PROOF_MAJOR) return fail(P2V_E_ARG, "P2V_FLAG_INPUT_TILED needs the in-place build (P2V_PROOF_MAJOR=1)");
-  // the lookahead transcript runs on its own stream and reads the batch in place; the transposing
-  // build's k_transpose writes v->soa on the caller's stream, which that stream does not wait for
-  if ((flags & P2V_FLAG_LOOKAHEAD) && !P2V_PROOF_MAJOR) return fail(P2V_E_ARG, "P2V_FLAG_LOOKAHEAD needs the in-place build (P2V_PROOF_MAJOR=1)");
   d.B = (int)((n + 63) / 64 * 64);
   const int64_t words = C.L.words;
   const uint64_t* src = proofs;
@@ -758,14 +745,7 @@ int p2v_verifier_run(p2v_verifier* v, const uint64_t* proofs, size_t n, int8_t* 
   // fault isolation (P2V_DEBUG_SYNC=1): each launch is named before it runs and waited for
 #define DBG(name, s_) do { if (v->debug_sync) { fprintf(stderr, "p2v: launched %s\n", name); fflush(stderr); \
     HCK(hipStreamSynchronize(s_)); HCK(hipGetLastError()); fprintf(stderr, "p2v: finished %s\n", name); fflush(stderr); } } while (0)
-#if P2V_PROOF_MAJOR
-  d.soa = src;   // kernels read the proof-major batch in place (devcommon.h ld()); no k_transpose
-#else
-  T0(0, st);
-  k_transpose<<<dim3((unsigned)((words + 63) / 64), NPB), 256, 0, st>>>(src, words, (int)n, (uint64_t*)v->soa.p, d.B);
-  DBG("k_transpose", st);
-  T1(0, st);
-#endif
+  d.soa = src;   // kernels read the caller's batch in place (devcommon.h ld())
   // phase 1: transcript waves + leaf-hash waves in one launch (the leaf sponges do not
   // depend on the challenges, so they fill the GPU while the serial transcripts run)
   // transcript form: the row form (16 lanes/proof) has the lowest latency, the quad form

@@ -8,6 +8,9 @@
 #define P2V_MAX_R 4
 #define P2V_LUT_CHUNK 16   // baby steps of the LUT evaluation
 #define P2V_LUT_PIECE 256  // chunks per k_lut work unit (4096 table entries)
+// launch shapes shared by api.cpp (the launch) and kernels.hip (__launch_bounds__, unit indexing)
+#define P2V_PLAN_WAVES 16  // waves per k_merkle_plan work-group (one global atomic per work-group and bucket)
+#define P2V_FIX_BLOCKS 256 // k_merkle_fix grid: its blocks wait for free slots beside the other batch's kernels
 
 struct DevCircuit {
   int32_t B;            // lane stride (batch padded to a multiple of 64)
@@ -71,7 +74,7 @@ struct DevCircuit {
   int32_t vcls[5];                 // item ranges of the vanishing kernel classes (Poseidon, coset, misc, lookup)
   const uint64_t* pos_w;           // PoseidonGate part 3: W = A'M [12][12] then k = A' rc [12] (vanish_poseidon.hip)
   // batch buffers
-  const uint64_t* soa;             // [words][B]
+  const uint64_t* soa;             // the caller's batch, read in place: [n][words], or 64-proof tiles (devcommon.h ld())
   uint64_t* chal;                  // [CH_WORDS][B]
   uint64_t* leafdig;               // [Q][T][4][B]
   uint8_t* mk_ok;                  // [Q][T][B]

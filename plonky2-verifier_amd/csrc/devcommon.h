@@ -8,14 +8,10 @@ namespace p2d {
 
 using gl::E;
 
-// Proof word w of lane p.  P2V_PROOF_MAJOR = 1 (default): the caller's proof-major batch
-// [n][words] read in place, lanes past n re-reading the last proof; every lane streams its own
-// proof's contiguous words, so the lines a load brings in serve the lane's next loads (measured:
-// +3 % proofs/s against 0, the transposed batch [word][B] written by an extra k_transpose pass
-// of 2 x 0.52 GB per 4 096 proofs, whose loads were coalesced 512-B rows)
-#ifndef P2V_PROOF_MAJOR
-#define P2V_PROOF_MAJOR 1
-#endif
+// Proof word w of lane p: the caller's proof-major batch [n][words] read in place, lanes past n
+// re-reading the last proof; every lane streams its own proof's contiguous words, so the lines a
+// load brings in serve the lane's next loads (+3 % proofs/s against the transposed batch [word][B]
+// of round 1: DESIGN.md §4 and "Retired build options").
 //
 // c.tiled (P2V_FLAG_INPUT_TILED, wave-uniform): the caller's batch in 64-proof tiles
 // [n/64][words][64], so the 64 lanes of a wave read one 512-B row per word: the same kernels with
@@ -23,13 +19,9 @@ using gl::E;
 // Both forms are affine in w, addr = base(p) + w * c.wstride (wstride 1 or 64, wave-uniform), so
 // a kernel keeps one per-lane base and a scalar step, as the proof-major form alone did.
 __device__ __forceinline__ uint64_t ld(const DevCircuit& c, int64_t w, int p) {
-#if P2V_PROOF_MAJOR
   const int64_t q = min(p, c.n - 1);
   const int64_t base = c.tiled ? (((q >> 6) * c.words) << 6) + (q & 63) : q * c.words;
   return c.soa[base + w * c.wstride];
-#else
-  return c.soa[w * c.B + p];
-#endif
 }
 __device__ __forceinline__ E lde(const DevCircuit& c, int64_t w, int p) { return E{ld(c, w, p), ld(c, w + 1, p)}; }
 __device__ __forceinline__ uint64_t& chal(const DevCircuit& c, int64_t w, int p) { return c.chal[w * c.B + p]; }

@@ -68,13 +68,6 @@ GL_HD uint64_t reduce96_nc(uint64_t hi, uint64_t lo) {
   return r;
 }
 
-#ifndef P2V_MUL_CMAD
-#define P2V_MUL_CMAD 1   // the product's carry-free MADs in plain C (no inline-asm SGPR outputs)
-#endif
-#ifndef P2V_MUL_PRODUCT
-#define P2V_MUL_PRODUCT 1   // device multiply's partial products: 1 = chained MAD addends (round 4), 0 = carry adds
-#endif
-
 #if defined(__HIP_DEVICE_COMPILE__)
 // gfx950 carry-chain primitives.  The compiler does not use the carry-out of
 // v_mad_u64_u32 / v_add_co_u32 and re-derives every carry with a 64-bit compare; these
@@ -84,13 +77,10 @@ GL_HD uint64_t reduce96_nc(uint64_t hi, uint64_t lo) {
 namespace ax {
 __device__ __forceinline__ uint64_t mad0(uint32_t a, uint32_t b) { uint64_t d, c; asm("v_mad_u64_u32 %0, %1, %2, %3, 0" : "=v"(d), "=s"(c) : "v"(a), "v"(b)); return d; }
 __device__ __forceinline__ uint64_t mad_co(uint32_t a, uint32_t b, uint64_t x, uint64_t& co) { uint64_t d; asm("v_mad_u64_u32 %0, %1, %2, %3, %4" : "=v"(d), "=s"(co) : "v"(a), "v"(b), "v"(x)); return d; }
-// a b + x where the caller guarantees no carry out of 64 bits
-__device__ __forceinline__ uint64_t mad_nc(uint32_t a, uint32_t b, uint64_t x) { uint64_t co; return mad_co(a, b, x, co); }
 __device__ __forceinline__ uint64_t madm1_co(uint32_t a, uint64_t x, uint64_t& co) { uint64_t d; asm("v_mad_u64_u32 %0, %1, %2, -1, %3" : "=v"(d), "=s"(co) : "v"(a), "v"(x)); return d; }
 __device__ __forceinline__ uint32_t add_co(uint32_t a, uint32_t b, uint64_t& co) { uint32_t d; asm("v_add_co_u32_e64 %0, %1, %2, %3" : "=v"(d), "=s"(co) : "v"(a), "v"(b)); return d; }
 __device__ __forceinline__ uint32_t addc_co(uint32_t a, uint32_t b, uint64_t ci, uint64_t& co) { uint32_t d; asm("v_addc_co_u32_e64 %0, %1, %2, %3, %4" : "=v"(d), "=s"(co) : "v"(a), "v"(b), "s"(ci)); return d; }
 __device__ __forceinline__ uint32_t addc0(uint32_t a, uint64_t ci) { uint32_t d; uint64_t co; asm("v_addc_co_u32_e64 %0, %1, %2, 0, %3" : "=v"(d), "=s"(co) : "v"(a), "s"(ci)); return d; }
-__device__ __forceinline__ uint32_t sub_co(uint32_t a, uint32_t b, uint64_t& co) { uint32_t d; asm("v_sub_co_u32_e64 %0, %1, %2, %3" : "=v"(d), "=s"(co) : "v"(a), "v"(b)); return d; }
 __device__ __forceinline__ uint32_t subb_co(uint32_t a, uint32_t b, uint64_t ci, uint64_t& co) { uint32_t d; asm("v_subb_co_u32_e64 %0, %1, %2, %3, %4" : "=v"(d), "=s"(co) : "v"(a), "v"(b), "s"(ci)); return d; }
 __device__ __forceinline__ uint32_t subb0_co(uint32_t a, uint64_t ci, uint64_t& co) { uint32_t d; asm("v_subb_co_u32_e64 %0, %1, %2, 0, %3" : "=v"(d), "=s"(co) : "v"(a), "s"(ci)); return d; }
 __device__ __forceinline__ uint32_t mask_m1(uint64_t m) { uint32_t d; asm("v_cndmask_b32_e64 %0, 0, -1, %1" : "=v"(d) : "s"(m)); return d; }
@@ -107,51 +97,34 @@ __device__ __forceinline__ uint32_t mask_1(uint64_t m) { uint32_t d; asm("v_cndm
 //   V = 1: one fix-up for the net wrap (14 VALU), branch-free: the general multiply;
 //   V = 2: the common +2^64 wrap by one MAD, the rare -2^64 wrap in a wave-uniform branch
 //          (12 VALU when not taken): the Poseidon S-box (p2::mul_nc);
-//   V = 0: one fix-up per wrap (16 VALU), the first form, kept for measurement.
+//   V = 3: as V = 2 without the branch: the caller gets the lanes that still need it (mul_nc_part).
+// (The first form, one fix-up per wrap, 16 VALU, is retired: DESIGN.md "Retired build options".)
 template <int V = 1>
 __device__ __forceinline__ uint64_t mul_nc_dev_v(uint64_t a, uint64_t b, uint64_t& negm) {
   using namespace ax;
   const uint32_t a0 = (uint32_t)a, a1 = (uint32_t)(a >> 32), b0 = (uint32_t)b, b1 = (uint32_t)(b >> 32);
-  uint64_t cm, c1, c2, ct, c4, bw1, bw2, bw3, bw4;
-#if P2V_MUL_PRODUCT == 1
+  static_assert(V >= 1 && V <= 3, "fix-up form");
+  uint64_t cm, ct, bw1, bw2;
   // the partial products chained through the MADs' 64-bit addends: every carry between the
   // 32-bit columns is absorbed by the next MAD, so no add-with-carry is needed
   //   x = a0 b1 + hi(a0 b0)          <= (2^32-1)^2 + 2^32 - 2 < 2^64
   //   y = a1 b0 + x = y + cm 2^64    (the column of weight 2^32; cm has weight 2^96)
   //   h = a1 b1 + hi(y)              <= (2^32-1)^2 + 2^32 - 1 < 2^64
   // product = lo(a0 b0) + lo(y) 2^32 + h 2^64 + cm 2^96: 4 MADs and 2 zero-extensions against
-  // 4 MADs and 3 carry adds (round 4)
-  (void)c1; (void)c2;
-#if P2V_MUL_CMAD
-  // the MADs whose carry-out is not needed in plain C: the compiler emits the same
+  // 4 MADs and 3 carry adds (round 4).
+  // The MADs whose carry-out is not needed in plain C: the compiler emits the same
   // v_mad_u64_u32 and, unlike after an inline-asm SGPR output, knows no wait state is needed
   const uint64_t p00 = (uint64_t)a0 * b0;
   const uint64_t x = (uint64_t)a0 * b1 + (p00 >> 32);
   const uint64_t y = mad_co(a1, b0, x, cm);
   const uint64_t hh = (uint64_t)a1 * b1 + (y >> 32);
-#else
-  const uint64_t p00 = mad0(a0, b0);
-  const uint64_t x = mad_nc(a0, b1, p00 >> 32);
-  const uint64_t y = mad_co(a1, b0, x, cm);
-  const uint64_t hh = mad_nc(a1, b1, y >> 32);
-#endif
   const uint32_t h0 = (uint32_t)hh, h1 = (uint32_t)(hh >> 32);          // + cm: below
   const uint64_t lo = ((uint64_t)(uint32_t)y << 32) | (uint32_t)p00;
-#else
-  const uint64_t p00 = mad0(a0, b0);
-  const uint64_t p01 = mad0(a0, b1);
-  const uint64_t m = mad_co(a1, b0, p01, cm);   // a0 b1 + a1 b0 = m + cm 2^64
-  const uint64_t p11 = mad0(a1, b1);
-  const uint32_t lo1 = add_co((uint32_t)(p00 >> 32), (uint32_t)m, c1);
-  const uint32_t h0 = addc_co((uint32_t)p11, (uint32_t)(m >> 32), c1, c2);
-  const uint32_t h1 = addc0((uint32_t)(p11 >> 32), c2);                 // + cm: below
-  const uint64_t lo = ((uint64_t)lo1 << 32) | (uint32_t)p00;
-#endif
   if constexpr (V == 2 || V == 3) {
   // as below, but the -2^64 case (only when the product has bits 64..95 zero and bits 0..63
   // below 2^32, e.g. powers of two) is a wave-uniform branch that is almost never taken.
   // V = 3: no branch here; the caller receives the lanes that still need it (mul_nc_part)
-  (void)c4; (void)bw3; (void)bw4;
+  uint64_t c4;
   const uint64_t t = madm1_co(h0, lo, ct);
   const uint32_t ul = subb_co((uint32_t)t, h1, cm, bw1);
   const uint32_t uh = subb0_co((uint32_t)(t >> 32), bw1, bw2);
@@ -160,11 +133,10 @@ __device__ __forceinline__ uint64_t mul_nc_dev_v(uint64_t a, uint64_t b, uint64_
   if constexpr (V == 3) { negm = neg; return r; }
   if (__builtin_expect(neg != 0, 0)) r = add64(r, ((uint64_t)mask_m1(neg) << 32) | sel(0u, 1u, neg));
   return r;
-  } else if constexpr (V == 1) {
+  } else {
   // lo + h0 (2^32 - 1) - (h1 + cm) = u + (c - b) 2^64 with the carry c of the MAD and the
   // borrow b of the subtraction; one fix-up for the net wrap: +2^64 == + (2^32 - 1), and
   // -2^64 == + p (mod 2^64 arithmetic), both without a second wrap.
-  (void)c4; (void)bw2; (void)bw3; (void)bw4;
   const uint64_t t = madm1_co(h0, lo, ct);
   const uint32_t ul = subb_co((uint32_t)t, h1, cm, bw1);
   const uint32_t uh = subb0_co((uint32_t)(t >> 32), bw1, bw2);
@@ -172,15 +144,6 @@ __device__ __forceinline__ uint64_t mul_nc_dev_v(uint64_t a, uint64_t b, uint64_
   const uint32_t kl = sel(sel(0u, 1u, neg), 0xFFFFFFFFu, pos);
   const uint32_t kh = mask_m1(neg);
   return add64(((uint64_t)uh << 32) | ul, ((uint64_t)kh << 32) | kl);
-  } else {
-  const uint64_t t = madm1_co(h0, lo, ct);                              // lo + h0 (2^32 - 1)
-  const uint32_t tl = add_co((uint32_t)t, mask_m1(ct), c4);             // wrapped: + 2^32 - 1
-  const uint32_t th = addc0((uint32_t)(t >> 32), c4);
-  const uint32_t rl = subb_co(tl, h1, cm, bw1);                         // - (h1 + cm) < 2^32
-  const uint32_t rh = subb0_co(th, bw1, bw2);
-  const uint32_t rl2 = sub_co(rl, mask_m1(bw2), bw3);                   // wrapped: - (2^32 - 1)
-  const uint32_t rh2 = subb0_co(rh, bw3, bw4);
-  return ((uint64_t)rh2 << 32) | rl2;
   }
 }
 template <int V = 1>

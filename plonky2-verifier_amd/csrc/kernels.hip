@@ -1,12 +1,11 @@
 // kernels.hip — gfx950 kernels of the batch verifier (everything except the vanishing /
 // gate-constraint kernel, which lives in vanish.hip).
 //
-// Data layout: the caller's proof-major batch ([n][words]) is read in place (devcommon.h ld();
-// P2V_PROOF_MAJOR=0 builds the older transposed [word][B] form).  In every kernel lane i of a
+// Data layout: the caller's proof-major batch ([n][words]) is read in place (devcommon.h ld()).
+// In every kernel lane i of a
 // wave handles proof (64*pb + i) and all other indices (query, tree, step, word) are
 // wave-uniform: control flow never diverges and the Poseidon round constants are scalar operands.
 //
-//   k_transpose   proof-major -> SoA (P2V_PROOF_MAJOR=0 only)
 //   k_phase1      transcript waves (a row or quad of lanes per proof, ~115 sequential permutations,
 //                 Challenge/Verifier.hs:58-103 + Challenge/FRI.hs:65-104) run in the SAME
 //                 launch as the leaf-hash waves (one lane per (proof, query, tree) sponge,
@@ -25,31 +24,7 @@
 using namespace p2d;
 using gl::E;
 
-// ------------------------------------------------------------------------ transpose
-extern "C" __global__ void __launch_bounds__(256) k_transpose(const uint64_t* __restrict__ in, int64_t words, int n,
-                                                              uint64_t* __restrict__ out, int B) {
-  __shared__ uint64_t tile[64][65];
-  const int64_t w0 = (int64_t)blockIdx.x * 64;
-  const int p0 = blockIdx.y * 64;
-  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;   // 64 x 4
-  for (int k = ty; k < 64; k += 4) {
-    int p = p0 + k; int64_t w = w0 + tx;
-    tile[k][tx] = (p < n && w < words) ? in[(int64_t)p * words + w] : 0;
-  }
-  __syncthreads();
-  for (int k = ty; k < 64; k += 4) {
-    int64_t w = w0 + k; int p = p0 + tx;
-    if (w < words) out[w * B + p] = tile[tx][k];
-  }
-}
-
 // ------------------------------------------------------------------------ helpers
-#ifndef P2V_LEAF_PREFETCH
-#define P2V_LEAF_PREFETCH 1   // leaf sponges: each block's words loaded one permutation ahead (0: two blocks per trip, round 5)
-#endif
-#ifndef P2V_LEAF_FOLD
-#define P2V_LEAF_FOLD 1   // the folded zh round 0 (poseidon.h P2V_ZH_FOLD) on each leaf's first block
-#endif
 __device__ __forceinline__ void leaf_hash_unit(const DevCircuit& c, int unit, int lane) {
   const int NPB = c.B >> 6;
   const int pb = unit % NPB, qt = unit / NPB;   // (position, query)-major: costly trees first
@@ -67,11 +42,10 @@ __device__ __forceinline__ void leaf_hash_unit(const DevCircuit& c, int unit, in
     for (int j = 0; j < 4; j++) if (j < len) st[j] = ld(c, off + j, p);
     len = 0;
   }
-#if P2V_LEAF_PREFETCH
   // sponge, overwrite mode, no padding.  One 8-word block per trip, its words loaded one
   // permutation ahead (during the previous block's permutation, into the registers that block has
   // just been copied out of), so no wave waits for its row at the top of a trip; one permutation
-  // call site (round 6)
+  // call site (round 6; the two-blocks-per-trip form of round 5: DESIGN.md "Retired build options")
   uint64_t nb[8];
 #pragma unroll
   for (int j = 0; j < 8; j++) nb[j] = j < len ? ld(c, off + j, p) : 0;
@@ -84,32 +58,8 @@ __device__ __forceinline__ void leaf_hash_unit(const DevCircuit& c, int unit, in
     // words the rest of the sponge reads: the digest (0..3) after the last block, else the
     // words the next block does not overwrite (nx.. 11); state words 8..11 are 0 in block 0
     const int nx = k - 8;
-    p2::permute_dev<P2V_LEAF_FOLD != 0>(st, i == 0, nx <= 0 ? 1 : (nx >= 8 ? 4 : ((7 << (nx >> 2)) & 7)));
+    p2::permute_dev<true>(st, i == 0, nx <= 0 ? 1 : (nx >= 8 ? 4 : ((7 << (nx >> 2)) & 7)));   // block 0: the folded zh round 0
   }
-#else
-  // sponge, overwrite mode, no padding.  Two 8-word blocks per trip, both loaded up front: each
-  // lane streams its own proof's row, so the loads of one trip cover a whole 128-B line while
-  // it is resident in L2 (one block per load left half of every line to be fetched again after
-  // the permutation, profiles/r02_fetch_calibration.json)
-  for (int i = 0; i < len; i += 16) {
-    const int k = len - i;
-    uint64_t nb[8];
-#pragma unroll
-    for (int j = 0; j < 8; j++) if (j < k) st[j] = ld(c, off + i + j, p);
-#pragma unroll
-    for (int j = 0; j < 8; j++) nb[j] = 8 + j < k ? ld(c, off + i + 8 + j, p) : 0;
-    // words the rest of the sponge reads: the digest (0..3) after the last block, else the
-    // words the next block does not overwrite (nx.. 11); state words 8..11 are 0 in block 0
-    int nx = k - 8;
-    p2::permute_dev<P2V_LEAF_FOLD != 0>(st, i == 0, nx <= 0 ? 1 : (nx >= 8 ? 4 : ((7 << (nx >> 2)) & 7)));
-    if (k > 8) {
-#pragma unroll
-      for (int j = 0; j < 8; j++) if (8 + j < k) st[j] = nb[j];
-      nx = k - 16;
-      p2::permute_dev<false>(st, false, nx <= 0 ? 1 : (nx >= 8 ? 4 : ((7 << (nx >> 2)) & 7)));
-    }
-  }
-#endif
   uint64_t* dst = c.leafdig + ((int64_t)(q * c.T + t) * 4) * c.B + p;
 #pragma unroll
   for (int i = 0; i < 4; i++) dst[(int64_t)i * c.B] = st[i];
@@ -155,27 +105,17 @@ __device__ __forceinline__ E horner_strided(const DevCircuit& c, int64_t off, in
 }
 
 // the row form's permutation: lposeidon.h (round 5: LDS exchange, merged partial blocks; 8.1-8.6 us
-// per dependent permutation against 11.7-12.3 us for the DPP form of rposeidon.h,
-// profiles/r05e_lrow_chain.txt; round 6: chain rows on the idle lanes, 6.6-6.8 us,
-// profiles/r06p_row_par.txt); P2V_ROW_LAT=0 rebuilds the DPP form
-#ifndef P2V_ROW_LAT
-#define P2V_ROW_LAT 1
-#endif
-#if P2V_ROW_LAT
-#define ROW_PERMUTE(x) lp::permute((x), LR, TL)
-#else
-#define ROW_PERMUTE(x) rp::permute((x), R, TQ)
-#endif
-__device__ __forceinline__ void transcript_row(const DevCircuit& c, int p, const rp::Row& R, const lp::Row& LR, const qp::TLds& TQ,
-                                               const lp::TLdsL& TL) {
-  (void)LR; (void)TQ; (void)TL;
+// per dependent permutation, profiles/r05e_lrow_chain.txt; round 6: chain rows on the idle lanes,
+// 6.6-6.8 us, profiles/r06p_row_par.txt; the DPP form it replaced: DESIGN.md "Retired build
+// options").  R: the row's DPP direction for the reduced openings' fold below (rposeidon.h)
+__device__ __forceinline__ void transcript_row(const DevCircuit& c, int p, const rp::Row& R, const lp::Row& LR, const lp::TLdsL& TL) {
   const int L = R.L;
   // public inputs hash, Hash/Sponge.hs:26-31 (sponge [] = zero digest)
   uint64_t x = 0;
   for (int i = 0; i < c.num_pis; i += 8) {
     const int k = c.num_pis - i;
     if (L < 8 && L < k) x = ld(c, c.pis + i + L, p);
-    x = ROW_PERMUTE(x);
+    x = lp::permute(x, LR, TL);
   }
   uint64_t pih[4];
 #pragma unroll
@@ -209,7 +149,7 @@ __device__ __forceinline__ void transcript_row(const DevCircuit& c, int p, const
         if (type == TOP_ABSORB_SOA) { if (mine) v = ld(c, (int64_t)a + j, p); }
         else if (type == TOP_ABSORB_PIH) { const int w = j & 3; v = w == 0 ? pih[0] : w == 1 ? pih[1] : w == 2 ? pih[2] : pih[3]; }
         else v = c.digest[j & 3];
-        if (nbuf == 8) { x = ROW_PERMUTE(x); nbuf = 0; }   // overwrite mode: the rate part is replaced
+        if (nbuf == 8) { x = lp::permute(x, LR, TL); nbuf = 0; }   // overwrite mode: the rate part is replaced
         if (mine) x = v;
         nbuf += take;
         k += take;
@@ -217,7 +157,7 @@ __device__ __forceinline__ void transcript_row(const DevCircuit& c, int p, const
       continue;
     }
     for (int k = 0; k < n; k++) {   // squeeze: output order state[7], state[6], ... (reverse of take 8)
-      if (absorbing || outpos < 0) { x = ROW_PERMUTE(x); absorbing = false; outpos = 7; }
+      if (absorbing || outpos < 0) { x = lp::permute(x, LR, TL); absorbing = false; outpos = 7; }
       uint64_t w = rp::get_word(x, outpos);
       outpos--;
       if (type == TOP_SQUEEZE_IDX) w &= qmask;
@@ -513,7 +453,7 @@ __device__ __forceinline__ void transcript_block(const DevCircuit& c, int tl, TL
     rp::init(R, threadIdx.x);
     lp::Row LR;
     lp::init(LR, U.l, threadIdx.x);
-    if ((g >> 4) < c.B) transcript_row(c, g >> 4, R, LR, T, U.l);
+    if ((g >> 4) < c.B) transcript_row(c, g >> 4, R, LR, U.l);
   } else {
     if ((g >> 2) < c.B) transcript_quad(c, g >> 2, g & 3, T);
   }
@@ -521,7 +461,7 @@ __device__ __forceinline__ void transcript_block(const DevCircuit& c, int tl, TL
 
 // the constant tables of the transcript form in use (tl uniform: 16 the row form, else quad)
 __device__ __forceinline__ void tlds_fill_form(TLdsAny& T, int tl) {
-  if (P2V_ROW_LAT && tl == 16) lp::tlds_fill(T.l, threadIdx.x, 256);
+  if (tl == 16) lp::tlds_fill(T.l, threadIdx.x, 256);
   else qp::tlds_fill(T.q, threadIdx.x, 256);
 }
 
@@ -628,21 +568,6 @@ __device__ __forceinline__ void merkle_level(uint64_t (&cur)[4], const uint64_t 
 #pragma unroll
   for (int i = 0; i < 4; i++) cur[i] = st[i];
 }
-// merkle_level, and the next level's siblings (when `more`, wave-uniform) loaded into sib before
-// the compression runs, so their latency hides behind it
-__device__ __forceinline__ void merkle_level_next(const DevCircuit& c, uint64_t (&cur)[4], uint64_t (&sib)[4], bool odd,
-                                                  bool more, int64_t nxt, int p) {
-  uint64_t st[12];
-#pragma unroll
-  for (int i = 0; i < 4; i++) { st[i] = odd ? sib[i] : cur[i]; st[4 + i] = odd ? cur[i] : sib[i]; st[8 + i] = 0; }
-  if (more) {
-#pragma unroll
-    for (int i = 0; i < 4; i++) sib[i] = ld(c, nxt + i, p);
-  }
-  p2::permute_dev(st, true, 1);
-#pragma unroll
-  for (int i = 0; i < 4; i++) cur[i] = st[i];
-}
 // cap_roots !! (idx >> depth) == the path's root
 __device__ __forceinline__ bool cap_ok(const DevCircuit& c, int t, uint32_t idx, const uint64_t (&cur)[4], int p) {
   bool ok = idx < (uint32_t)c.cap_len;
@@ -712,21 +637,12 @@ extern "C" __global__ void __launch_bounds__(256) P2V_MERKLE_ATTR k_merkle(DevCi
 //   k_merkle_fix      the flagged followers (a compact list; none for honest proofs)
 //   k_merkle_resolve  one lane per (tree, query, proof): a follower takes the status of its
 //                     first flagged or root ancestor
-#ifndef P2V_CSE_PREFETCH
-#define P2V_CSE_PREFETCH 0   // k_merkle_cse: 1 loads each level's siblings one compression ahead (96 VGPRs; measured no gain, profiles/r06l_prefetch.txt)
-#endif
-#ifndef P2V_CSE_ORDER
-#define P2V_CSE_ORDER 0   // k_merkle_cse wave order: 0 bucket-major, longest first; 1 tile order merged over the buckets, XCD ranges (round 6, measured slower: see cse_wave)
-#endif
 #define P2V_CSE_CSTRIDE 16   // counters 64 B apart: atomics on one line serialise
 __device__ __forceinline__ void class_shape(const DevCircuit& c, int cls, int& sh, int& depth) {
   sh = 0; depth = c.depth0;
   if (cls > 0) { for (int j = 0; j < cls; j++) sh += c.arity[j]; depth = c.step_depth[cls - 1]; }
 }
 __device__ __forceinline__ int tree_class(int t) { return t < 4 ? 0 : t - 3; }
-#ifndef P2V_PLAN_WAVES
-#define P2V_PLAN_WAVES 16   // waves per k_merkle_plan work-group (one global atomic per work-group and bucket)
-#endif
 extern "C" __global__ void __launch_bounds__(64 * P2V_PLAN_WAVES) k_merkle_plan(DevCircuit c) {
   __shared__ int hist[P2V_CSE_MAX_DEPTH + 1], gbase[P2V_CSE_MAX_DEPTH + 1];
   const int lane = threadIdx.x & 63;
@@ -736,13 +652,7 @@ extern "C" __global__ void __launch_bounds__(64 * P2V_PLAN_WAVES) k_merkle_plan(
   if (threadIdx.x < (unsigned)nb) hist[threadIdx.x] = 0;
   __syncthreads();
   const bool unit_live = unit < ncls * c.Q * NPB;   // wave-uniform
-  // tile-major (P2V_CSE_ORDER 1): a work-group's units are (tree class, query) pairs of one or two
-  // 64-proof tiles, so the buckets fill tile by tile and k_merkle_cse's merged order follows the tiles
-#if P2V_CSE_ORDER
-  const int cq = unit % (ncls * c.Q), pb = unit / (ncls * c.Q);
-#else
   const int pb = unit % NPB, cq = unit / NPB;
-#endif
   const int q = cq % c.Q, cls = unit_live ? cq / c.Q : 0;
   const int p = pb * 64 + lane;
   const bool live = unit_live && p < c.n;
@@ -835,21 +745,12 @@ __device__ __forceinline__ void cse_flag(const DevCircuit& c, int t, int q, int 
   if (at < c.mcap) c.mfix[at] = (uint32_t)t << 27 | (uint32_t)q << 22 | (uint32_t)p;
   else c.mk_ok[(int64_t)(q * c.T + t) * c.B + p] = 0;
 }
-#ifndef P2V_CSE_INLINE
-#define P2V_CSE_INLINE 0   // 1: a follower failing (A) / (C) re-runs its path in k_merkle_cse, not k_merkle_fix
-#endif
-// Which chains a wave of k_merkle_cse runs: bucket b (the chain length) and wave w of that bucket.
-// P2V_CSE_ORDER 0 (round 5): bucket-major, longest first.  The 64 lanes of a wave are then runs of
-// a few proofs from many 64-proof tiles, and the other proofs of every 128-B line they read sit in
-// other buckets, read long after the line has left the XCD's L2: 6.6x the algorithmic bytes
-// (profiles/r05z_pmc_traffic.json).  P2V_CSE_ORDER 1: the waves of all buckets
-// merged in the order of the plan's tiles (the plan appends tile by tile), so every chain that
-// reads a tile's rows -- all lengths, the owners' and followers' checks -- runs at about the same
-// time, and each XCD takes one contiguous range of that order (blocks i, i + 8, ... share an XCD,
-// MI355X_MICROARCH.md "Workgroup dispatch"), so those reads meet in one L2.  The merge is fraction
-// r of every bucket in turn: waves [r nw_b / R, (r + 1) nw_b / R) of bucket b, longest first within
-// a fraction; fraction r starts at sum_b floor(r nw_b / R), found by bisection.  Scalar work only.
-#define P2V_CSE_LR 12   // R = 4096 fractions
+// Which chains a wave of k_merkle_cse runs: bucket b (the chain length) and wave w of that bucket,
+// bucket-major, longest first.  The 64 lanes of a wave are then runs of a few proofs from many
+// 64-proof tiles, and the other proofs of every 128-B line they read sit in other buckets, read long
+// after the line has left the XCD's L2: 6.6x the algorithmic bytes (profiles/r05z_pmc_traffic.json,
+// VERDICT r5 item 1; the tile-merged order that addressed it measured slower: DESIGN.md "Retired
+// build options").
 __device__ __forceinline__ bool cse_wave(const DevCircuit& c, int& b, int64_t& w) {
   const int nbk = c.depth0 + 1;
   uint64_t nw[P2V_CSE_MAX_DEPTH + 1];
@@ -860,33 +761,6 @@ __device__ __forceinline__ bool cse_wave(const DevCircuit& c, int& b, int64_t& w
     total += nw[k];
   }
   const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-#if P2V_CSE_ORDER
-  const uint64_t nblk = gridDim.x >> 3;   // the grid is a multiple of 8
-  const uint64_t g = ((uint64_t)(blockIdx.x & 7) * nblk + (blockIdx.x >> 3)) * 4 + wv;
-  if (g >= total) return false;
-  auto start = [&](uint64_t r) {
-    uint64_t s = 0;
-#pragma unroll
-    for (int k = 0; k <= P2V_CSE_MAX_DEPTH; k++) s += (r * nw[k]) >> P2V_CSE_LR;
-    return s;
-  };
-  uint64_t r = 0;
-  for (int step = P2V_CSE_LR - 1; step >= 0; step--) {
-    const uint64_t rr = r | (1ull << step);
-    if (start(rr) <= g) r = rr;
-  }
-  uint64_t off = g - start(r);   // < start(r + 1) - start(r): fraction r holds wave g
-  b = -1;
-#pragma unroll
-  for (int k = P2V_CSE_MAX_DEPTH; k >= 0; k--) {
-    const uint64_t lo = (r * nw[k]) >> P2V_CSE_LR, len = (((r + 1) * nw[k]) >> P2V_CSE_LR) - lo;
-    if (b < 0) {
-      if (off < len) { b = k; w = (int64_t)(lo + off); }
-      else off -= len;
-    }
-  }
-  return b >= 0;
-#else
   int64_t g = (int64_t)blockIdx.x * 4 + wv;
 #pragma unroll
   for (int k = P2V_CSE_MAX_DEPTH; k >= 0; k--) {   // longest chains first
@@ -894,7 +768,6 @@ __device__ __forceinline__ bool cse_wave(const DevCircuit& c, int& b, int64_t& w
     g -= (int64_t)nw[k];
   }
   return g < 0;
-#endif
 }
 __device__ __forceinline__ void merkle_chain(const DevCircuit& c) {
   const int lane = threadIdx.x & 63;
@@ -914,21 +787,10 @@ __device__ __forceinline__ void merkle_chain(const DevCircuit& c) {
   tree_path(c, t, q, p, depth, poff, idx);
   uint64_t cur[4];
   load_leafdig(c, t, q, p, cur);
-#if P2V_CSE_PREFETCH
-  // each level's siblings are loaded one compression ahead, into the registers the compression
-  // has just consumed, so no wave waits for them at the top of a level
-  uint64_t sib[4];
-  if (e > 0) {
-#pragma unroll
-    for (int i = 0; i < 4; i++) sib[i] = ld(c, poff + i, p);
-  }
-#endif
   for (int l = 0; l < e; l++) {
-#if !P2V_CSE_PREFETCH
     uint64_t sib[4];
 #pragma unroll
     for (int i = 0; i < 4; i++) sib[i] = ld(c, poff + 4 * l + i, p);
-#endif
     const int f = (int)((fol >> (5 * l)) & 31);
     if (f != 31) {   // (B): the follower meeting this path here holds this node as its sibling
       const int64_t fo = poff + (int64_t)(f - q) * c.qstride + 4 * l;
@@ -937,11 +799,7 @@ __device__ __forceinline__ void merkle_chain(const DevCircuit& c) {
       for (int i = 0; i < 4; i++) bad |= ld(c, fo + i, p) != cur[i];
       if (bad) cse_flag(c, t, f, p);
     }
-#if P2V_CSE_PREFETCH
-    merkle_level_next(c, cur, sib, idx & 1u, l + 1 < e, poff + 4 * (l + 1), p);
-#else
     merkle_level(cur, sib, idx & 1u);
-#endif
     idx >>= 1;
   }
   if (e == depth) {
@@ -968,21 +826,7 @@ __device__ __forceinline__ void merkle_chain(const DevCircuit& c) {
   for (int l = l0; l < depth; l++)   // (C)
 #pragma unroll
     for (int i = 0; i < 4; i++) bad |= ld(c, poff + 4 * l + i, p) != ld(c, oo + 4 * l + i, p);
-#if P2V_CSE_INLINE
-  if (bad) {   // this lane's own data disagrees: its own path to the cap, here (k_merkle_resolve skips it)
-    (void)cse_flag_once(c, t, q, p);   // (an entry (B) listed first re-runs the same path in k_merkle_fix)
-    for (int l = e; l < depth; l++) {
-      uint64_t sib[4];
-#pragma unroll
-      for (int i = 0; i < 4; i++) sib[i] = ld(c, poff + 4 * l + i, p);
-      merkle_level(cur, sib, idx & 1u);
-      idx >>= 1;
-    }
-    c.mk_ok[(int64_t)(q * c.T + t) * c.B + p] = cap_ok(c, t, idx, cur, p) ? 1 : 0;
-  }
-#else
   if (bad) cse_flag(c, t, q, p);
-#endif
 }
 #ifndef P2V_CSE_WAVES
 #define P2V_CSE_WAVES 5   // amdgpu_waves_per_eu on k_merkle_cse: 90 VGPRs, no spills; 6 (80 VGPRs, 40 B of spills
@@ -1031,13 +875,11 @@ extern "C" __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_pe
   if ((int64_t)blockIdx.x * 16 >= nfix) return;   // block-uniform: no entry for this block's rows (honest batches: all)
   tlds_fill_form(T, 16);
   __builtin_amdgcn_s_setprio(3);
-  rp::Row R;
+  rp::Row R;   // only R.L is read; dropping the init changes this kernel's register allocation (rposeidon.h)
   rp::init(R, threadIdx.x);
   lp::Row LR;
   lp::init(LR, T.l, threadIdx.x);
-  const qp::TLds& TQ = T.q;
   const lp::TLdsL& TL = T.l;
-  (void)LR; (void)TQ; (void)TL;
   const int L = R.L;
   const int64_t rows = (int64_t)gridDim.x * 16;
   for (int64_t k = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 4; k < nfix; k += rows) {   // row-uniform
@@ -1061,7 +903,7 @@ extern "C" __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_pe
       const uint64_t cb = L == 4 ? c0 : L == 5 ? c1 : L == 6 ? c2 : c3;
       const bool odd = idx & 1u;
       const uint64_t x = L < 4 ? (odd ? sib : cur) : L < 8 ? (odd ? cb : sib) : 0;
-      cur = ROW_PERMUTE(x);
+      cur = lp::permute(x, LR, TL);
       idx >>= 1;
     }
     bool ok = idx < (uint32_t)c.cap_len;
@@ -1118,14 +960,10 @@ extern "C" __global__ void __launch_bounds__(256) k_merkle_row(DevCircuit c) {
   __shared__ TLdsAny T;
   tlds_fill_form(T, 16);
   __builtin_amdgcn_s_setprio(3);   // the batch's critical path in this mode
-  rp::Row R;
-  rp::init(R, threadIdx.x);
   lp::Row LR;
   lp::init(LR, T.l, threadIdx.x);
-  const qp::TLds& TQ = T.q;
   const lp::TLdsL& TL = T.l;
-  (void)LR; (void)TQ; (void)TL;
-  const int L = R.L;
+  const int L = LR.L;
   const int path = (int)((blockIdx.x * 256 + threadIdx.x) >> 4);
   const int npaths = c.Q * c.T * c.n;
   const bool live = path < npaths;   // idle rows still run the permutation (its DPP ops span the row)
@@ -1149,7 +987,7 @@ extern "C" __global__ void __launch_bounds__(256) k_merkle_row(DevCircuit c) {
     const uint64_t cb = L == 4 ? c0 : L == 5 ? c1 : L == 6 ? c2 : c3;
     const bool odd = idx & 1u;
     const uint64_t x = L < 4 ? (odd ? sib : cur) : L < 8 ? (odd ? cb : sib) : 0;
-    cur = ROW_PERMUTE(x);   // lanes 0..3: the compression's output
+    cur = lp::permute(x, LR, TL);   // lanes 0..3: the compression's output
     idx >>= 1;
   }
   bool ok = idx < (uint32_t)c.cap_len;
@@ -1302,12 +1140,6 @@ __device__ __forceinline__ E reduce_powers(const DevCircuit& c, const Segs& S, i
 
 // k_fri runs on the side stream beside k_merkle (see vanish.hip P2V_SIDE_WAVES): 5 waves per SIMD
 // caps it at 96 VGPRs, so a wave fits where one k_merkle wave retired (0: compiler default, 122)
-#ifndef P2V_FOLD16_HALVES
-#define P2V_FOLD16_HALVES 1
-#endif
-#ifndef P2V_FRI_CHUNKED
-#define P2V_FRI_CHUNKED 1   // combineInitial in chunks of 8 with unreduced product sums (round 5, above)
-#endif
 #ifndef P2V_FRI_WAVES
 #define P2V_FRI_WAVES 5
 #endif
@@ -1333,8 +1165,7 @@ extern "C" __global__ void __launch_bounds__(256) P2V_FRI_ATTR k_fri(DevCircuit 
   // quotient, lookup part; secondBatch = first r of the pp part, lookup part.
   const int npp_all = r * ((c.num_routed + c.qdf - 1) / c.qdf);
   const int64_t l0 = base + c.leaf[0], l1 = base + c.leaf[1], l2 = base + c.leaf[2], l3 = base + c.leaf[3];
-#if P2V_FRI_CHUNKED
-  // ascending lists (the Horner of round 4 below walks them from the top): firstBatch =
+  // ascending lists: firstBatch =
   // leaf0 | leaf1 | leaf2[0, npp_all) | leaf3 | leaf2[npp_all, w2); secondBatch = leaf2[0, r') |
   // leaf2[npp_all, w2)
   E ap[9];
@@ -1346,16 +1177,6 @@ extern "C" __global__ void __launch_bounds__(256) P2V_FRI_ATTR k_fri(DevCircuit 
   Segs s1{{l2, l2 + npp_all, 0, 0, 0}, {rr, c.width[2] - npp_all, 0, 0, 0}, 2};
   const E g0 = reduce_powers(c, s0, p, alpha, ap);
   const E g1 = reduce_powers(c, s1, p, alpha, ap);
-#else
-  E g0 = gl::e0(), g1 = gl::e0();
-  for (int i = c.width[2] - 1; i >= npp_all; i--) g0 = gl::eadd(gl::emul(g0, alpha), gl::eb(ld(c, l2 + i, p)));
-  for (int i = c.width[3] - 1; i >= 0; i--) g0 = gl::eadd(gl::emul(g0, alpha), gl::eb(ld(c, l3 + i, p)));
-  for (int i = npp_all - 1; i >= 0; i--) g0 = gl::eadd(gl::emul(g0, alpha), gl::eb(ld(c, l2 + i, p)));
-  for (int i = c.width[1] - 1; i >= 0; i--) g0 = gl::eadd(gl::emul(g0, alpha), gl::eb(ld(c, l1 + i, p)));
-  for (int i = c.width[0] - 1; i >= 0; i--) g0 = gl::eadd(gl::emul(g0, alpha), gl::eb(ld(c, l0 + i, p)));
-  for (int i = c.width[2] - 1; i >= npp_all; i--) g1 = gl::eadd(gl::emul(g1, alpha), gl::eb(ld(c, l2 + i, p)));
-  for (int i = (r < npp_all ? r : npp_all) - 1; i >= 0; i--) g1 = gl::eadd(gl::emul(g1, alpha), gl::eb(ld(c, l2 + i, p)));
-#endif
   const int len2 = (r < npp_all ? r : npp_all) + (c.width[2] - npp_all);
   const uint64_t px = gl::mul(gl::MULT_GEN, pow_root(c, c.lde_bits, gl::rev_bits(c.lde_bits, idx)));
   const uint64_t omega = c.root_pow2[32 - c.degree_bits];
@@ -1386,7 +1207,7 @@ extern "C" __global__ void __launch_bounds__(256) P2V_FRI_ATTR k_fri(DevCircuit 
       case 1: nv = fold_regs<1>(c, s, eoff, p, bo); break;
       case 2: nv = fold_regs<2>(c, s, eoff, p, bo); break;
       case 3: nv = fold_regs<3>(c, s, eoff, p, bo); break;
-      case 4: nv = P2V_FOLD16_HALVES ? fold16_halves(c, s, eoff, p, bo) : fold_regs<4>(c, s, eoff, p, bo); break;
+      case 4: nv = fold16_halves(c, s, eoff, p, bo); break;
       default: nv = fold_generic(c, s, ab, eoff, p, bo); break;
     }
     cur = nv;
@@ -1460,7 +1281,7 @@ extern "C" __global__ void __launch_bounds__(256) k_status(DevCircuit c, int8_t*
 // (the permutation's row reduction with its grouped carry fix-up).  One lane per item.
 // ops 5-8: the S-box forms x -> x^7 (Hash/Poseidon.hs:92-96) with their rare -2^64 fix-ups
 // (ADVICE r4): 5 sbox_n<1> (throughput permutation, partial rounds), 6 sbox_n<2> on the pair
-// (a[i], b[i]) (full rounds; out[2i], out[2i+1]), 7 sbox_lat_br (row form), 8 sbox_lat (quad /
+// (a[i], b[i]) (full rounds; out[2i], out[2i+1]), 7 sbox_lat_br (the retired DPP row form's), 8 sbox_lat (quad /
 // pair forms); canonical outputs.
 extern "C" __global__ void __launch_bounds__(256) k_selftest(int op, const uint64_t* a, const uint64_t* b, uint64_t* out, int64_t n) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1486,13 +1307,9 @@ extern "C" __global__ void __launch_bounds__(256) k_selftest(int op, const uint6
     uint64_t st[12], t[12], kl[12], kh[12];
 #pragma unroll
     for (int k = 0; k < 12; k++) { st[k] = a[12 * i + k]; kl[k] = b[k]; kh[k] = b[12 + k]; }
-#if P2V_MDS_BRANCH == 2
     p2::dv::mds_group<0>(st, t, kl, kh);
     p2::dv::mds_group<4>(st, t, kl, kh);
     p2::dv::mds_group<8>(st, t, kl, kh);
-#else
-    p2::dv::mds_rows<0, 12>(st, t, kl, kh);
-#endif
 #pragma unroll
     for (int k = 0; k < 12; k++) out[12 * i + k] = t[k];
 #endif
@@ -1508,7 +1325,7 @@ extern "C" __global__ void __launch_bounds__(256) k_selftest(int op, const uint6
 }
 
 // The latency forms of the permutation on caller-chosen states (p2v_selftest ops 9-11; ADVICE
-// r4): 9 the row form (lposeidon.h, or rposeidon.h with P2V_ROW_LAT=0; 16 lanes per state), 10 the quad form (qposeidon.h, 4 lanes),
+// r4): 9 the row form (lposeidon.h; 16 lanes per state), 10 the quad form (qposeidon.h, 4 lanes),
 // 11 the pair form (pposeidon.h, 2 lanes).  Every lane of a group takes part in the DPP moves, so
 // lanes past n compute on a copy of state n - 1 and store nothing.  a, out: n states of 12 words.
 extern "C" __global__ void __launch_bounds__(256) k_selftest_forms(int op, const uint64_t* a, uint64_t* out, int64_t n) {
@@ -1522,15 +1339,10 @@ extern "C" __global__ void __launch_bounds__(256) k_selftest_forms(int op, const
   const uint64_t* s = a + 12 * src;
   uint64_t* o = out + 12 * item;
   if (op == 9) {
-    rp::Row R;
-    rp::init(R, threadIdx.x);
     lp::Row LR;
     lp::init(LR, T.l, threadIdx.x);
-    const qp::TLds& TQ = T.q;
-    const lp::TLdsL& TL = T.l;
-    (void)LR; (void)TQ; (void)TL;
-    const uint64_t x = ROW_PERMUTE(R.L < 12 ? s[R.L] : 0);
-    if (item < n && R.L < 12) o[R.L] = x;
+    const uint64_t x = lp::permute(LR.L < 12 ? s[LR.L] : 0, LR, T.l);
+    if (item < n && LR.L < 12) o[LR.L] = x;
   } else if (op == 10) {
     uint64_t x[3] = {s[3 * t], s[3 * t + 1], s[3 * t + 2]};
     qp::permute(x, t, T.q);

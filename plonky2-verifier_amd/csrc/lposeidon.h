@@ -2,7 +2,7 @@
 // transcript of small batches (~115 strictly dependent permutations per proof,
 // Challenge/Pure.hs:50-69) and the small-batch Merkle paths (Hash/Merkle.hs:27-42).
 //
-// Same layout and interface as rposeidon.h (lane L < 12 of the row holds state word L), built
+// Lane L < 12 of the row holds state word L (the DPP helpers around it: rposeidon.h).  Built
 // for a lone wave: on a dependent chain a wave issues about one instruction per 4-cycle slot
 // whatever their independence, so its time is its instruction count, s_nop padding included
 // (DESIGN.md §5.2).  Round 5 cut that count:
@@ -169,61 +169,6 @@ __device__ __forceinline__ uint64_t full_round(uint64_t x, int r, const Row& R, 
   return red_small(al, ah);
 }
 
-// D merged partial rounds (poseidon.h PBlock / dv::pblock): x = this lane's word of the state
-// entering the block (its constants included) -> its word of the state after the block
-template <int D>
-__device__ __forceinline__ uint64_t pblock(uint64_t x, const p2::PBlock& B, const Row& R, const TLdsL& T) {
-  uint64_t s[12], y[D + 1];
-  exchange(x, R.xb, R.L, s);
-  s[0] = sbox(s[0]);   // y_1, word 0 of s'
-  const uint32_t m00 = T.m[0][0];
-  {   // chain row 1: row 0 of M s' + d_1
-    uint64_t al = B.dlo[0], ah = B.dhi[0];
-    dot12(T.m[0], s, al, ah);
-    y[2] = sbox(red_small(al, ah));
-  }
-  if constexpr (D >= 3) {   // chain row 2: G_2 row 0 . s' + M00 y_2 + d_2
-    uint64_t al = madr((uint32_t)y[2], m00, B.dlo[1]), ah = madr((uint32_t)(y[2] >> 32), m00, B.dhi[1]);
-    dot12(B.cf[0], s, al, ah);
-    y[3] = sbox(red_small(al, ah));
-  }
-  if constexpr (D >= 4) {   // chain row 3: G_3 row 0 . s' + H_3[0][2] y_2 + M00 y_3 + d_3
-    uint64_t al = madr((uint32_t)y[3], m00, B.dlo[2]), ah = madr((uint32_t)(y[3] >> 32), m00, B.dhi[2]);
-    dot12(B.cf[1], s, al, ah);
-    al = madr((uint32_t)y[2], B.cf[1][12], al);
-    ah = madr((uint32_t)(y[2] >> 32), B.cf[1][12], ah);
-    y[4] = sbox(red_small(al, ah));
-  }
-  // this lane's output row: G_D row Lc . s' + sum_m H_D[Lc][m] y_m + M[Lc][0] y_D + d_D
-  const uint32_t* cf = B.cf[2 + R.Lc];
-  const uint32_t c0 = T.m[R.Lc][0];
-  uint64_t al = madr((uint32_t)y[D], c0, B.dlo[4 + R.Lc]), ah = madr((uint32_t)(y[D] >> 32), c0, B.dhi[4 + R.Lc]);
-  dot12(cf, s, al, ah);
-#pragma unroll
-  for (int m = 2; m < D; m++) {
-    al = madr((uint32_t)y[m], cf[12 + m - 2], al);
-    ah = madr((uint32_t)(y[m] >> 32), cf[12 + m - 2], ah);
-  }
-  return D == 4 ? red_wide(al, ah) : red_small(al, ah);
-}
-
-// Round 6: the same block with its chain rows on the row's idle lanes.  pblock above evaluates
-// chain row k (a 12-term dot product over s') between S-box k and S-box k + 1, so three dot
-// products sit on the lone wave's serial path per block.  None of them depends on the chain
-// except through its y terms.  Here every lane of the row evaluates one row's s'-part in the same
-// dot product: lanes 0..11 their output rows, lanes 12, 13, 14 chain rows 1, 2, 3.  Then the
-// chain is, per S-box, one reduction in every lane, a broadcast of the chain lane's value to its
-// row (DPP row_newbcast) and the S-box.  Each lane adds y_m times its own row's coefficient:
-//   output row L: H_D[L][m] (cf[12 + m - 2]) for m < D, M[L][0] for m = D;
-//   chain row 2 (lane 13): M[0][0] for y_2;  chain row 3 (lane 14): H_3[0][2] (cf[12]) for y_2,
-//   M[0][0] for y_3.
-// A lane's sum is read only at the step where it is complete (lane 12 at S-box 2, 13 at 3, 14 at
-// 4, the output rows after the block).  That sum has the same non-negative terms as pblock's, so
-// the same reduction bounds hold.  The other lanes' reductions of partial sums are never read.
-// Lane 15 repeats lane 13's row and is never read.
-#ifndef P2V_ROW_PAR
-#define P2V_ROW_PAR 1   // 0: pblock (round 5), the chain rows between the S-boxes
-#endif
 // lane S of each 16-lane row, to the whole row (DPP row_newbcast: a VALU move, no LDS round trip)
 template <int S>
 __device__ __forceinline__ uint64_t row_bcast(uint64_t v) {
@@ -237,22 +182,30 @@ __device__ __forceinline__ uint64_t row_bcast(uint64_t v) {
 // serial path instead of four.  Bit-identical to sbox(): mul_lat's result is a function of the
 // 128-bit product alone (the cross terms a0 b1 + a1 b0 enter as one sum), so x^3 x^4 and x^4 x^3
 // agree.
-#ifndef P2V_ROW_SBOX2
-#define P2V_ROW_SBOX2 1   // 0: sbox() for the uniform S-box inputs too
-#endif
 __device__ __forceinline__ uint64_t sbox_u(uint64_t x, int L) {
-#if P2V_ROW_SBOX2
   const uint64_t x2 = mul_lat(x, x);
   const uint64_t h = mul_lat((L & 1) ? x2 : x, x2);
   constexpr int kSwap = 1 | (0 << 2) | (3 << 4) | (2 << 6);
   const uint32_t olo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)h, kSwap, 0xf, 0xf, false);
   const uint32_t ohi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(h >> 32), kSwap, 0xf, 0xf, false);
   return mul_lat(h, (uint64_t)ohi << 32 | olo);
-#else
-  (void)L;
-  return sbox(x);
-#endif
 }
+// D merged partial rounds (poseidon.h PBlock / dv::pblock): x = this lane's word of the state
+// entering the block (its constants included) -> its word of the state after the block, with the
+// chain rows on the row's idle lanes (round 6).  Chain row k is a 12-term dot product over s' that
+// depends on the chain only through its y terms; evaluated between S-box k and S-box k + 1
+// (round 5) three dot products sat on the lone wave's serial path per block.  Here every lane of
+// the row evaluates one row's s'-part in the same dot product: lanes 0..11 their output rows,
+// lanes 12, 13, 14 chain rows 1, 2, 3.  Then the
+// chain is, per S-box, one reduction in every lane, a broadcast of the chain lane's value to its
+// row (DPP row_newbcast) and the S-box.  Each lane adds y_m times its own row's coefficient:
+//   output row L: H_D[L][m] (cf[12 + m - 2]) for m < D, M[L][0] for m = D;
+//   chain row 2 (lane 13): M[0][0] for y_2;  chain row 3 (lane 14): H_3[0][2] (cf[12]) for y_2,
+//   M[0][0] for y_3.
+// A lane's sum is read only at the step where it is complete (lane 12 at S-box 2, 13 at 3, 14 at
+// 4, the output rows after the block).  That sum has the same non-negative terms as dv::pblock's,
+// so the same reduction bounds hold.  The other lanes' reductions of partial sums are never read.
+// Lane 15 repeats lane 13's row and is never read.
 template <int D>
 __device__ __forceinline__ uint64_t pblock_par(uint64_t x, const p2::PBlock& B, const Row& R, const TLdsL& T, uint32_t c0) {
   uint64_t s[12];
@@ -287,18 +240,10 @@ __device__ __forceinline__ uint64_t permute(uint64_t x, const Row& R, const TLds
   x = p2::add_nc(x, T.rc0[R.Lc]);
 #pragma unroll 1
   for (int r = 0; r < 4; r++) x = full_round(x, r, R, T);
-#if P2V_PMERGE == 4 && P2V_ROW_PAR
   const uint32_t c0 = T.m[R.Lc][0];   // M[L][0]: the output row's y_D coefficient
 #pragma unroll 1
   for (int b = 0; b < 5; b++) x = pblock_par<4>(x, T.pm[b], R, T, c0);
   x = pblock_par<2>(x, T.pm[5], R, T, c0);
-#elif P2V_PMERGE == 4
-#pragma unroll 1
-  for (int b = 0; b < 5; b++) x = pblock<4>(x, T.pm[b], R, T);
-  x = pblock<2>(x, T.pm[5], R, T);
-#else
-#error "lposeidon.h follows the D = 4,4,4,4,4,2 merge schedule (P2V_PMERGE 4)"
-#endif
 #pragma unroll 1
   for (int r = 26; r < 30; r++) x = full_round(x, r, R, T);
   return gl::canon(x);

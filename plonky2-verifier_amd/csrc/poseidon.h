@@ -10,16 +10,6 @@
 #include "gl.h"
 #include "poseidon_constants.h"
 #include "pasm.h"
-#ifndef P2V_POSEIDON_ASMBLK
-#define P2V_POSEIDON_ASMBLK 0   // measured: no faster in the verifier kernels (VGPR pressure), see DESIGN.md §5.1
-#endif
-
-#ifndef P2V_MDS_BRANCH
-#define P2V_MDS_BRANCH 2   // MDS row reduction: the rare carry fix-up in a uniform branch (1: per row, 2: per group of 4 rows)
-#endif
-#ifndef P2V_SBOX_MUL
-#define P2V_SBOX_MUL 2   // S-box multiply form (gl::mul_nc_dev_v): 2 = rare wrap as a uniform branch
-#endif
 
 namespace p2 {
 
@@ -50,19 +40,20 @@ __host__ __device__ __forceinline__ uint64_t add_nc(uint64_t a, uint64_t b) {   
 }
 __host__ __device__ __forceinline__ uint64_t mul_nc(uint64_t a, uint64_t b) {
 #if defined(__HIP_DEVICE_COMPILE__)
-  return gl::mul_nc_dev_v<P2V_SBOX_MUL>(a, b);
+  return gl::mul_nc_dev_v<2>(a, b);   // the S-box multiply: the rare wrap as a uniform branch
 #else
   uint64_t hi, lo;
   gl::mul128(a, b, hi, lo);
   return gl::reduce128_nc(hi, lo);
 #endif
 }
-// x^7, latency forms for the transcript chains (qposeidon.h, rposeidon.h, pposeidon.h).
+// x^7, latency forms for the transcript chains (qposeidon.h, pposeidon.h).
+// sbox_lat: the branch-free multiply (14 VALU), straight-line code (with the branch form the quad
+// form's k_phase1 went 1.93 -> 2.03 ms, profiles/r04u_sbox_lat_branch.txt).
 // sbox_lat_br: the S-box multiply (11 VALU) with its rare -2^64 fix-up behind one wave-uniform
-// branch per stage (x^2; x^3 and x^4; x^7), as the throughput S-box (sbox_n); the row form
-// (rposeidon.h) uses it (k_merkle_row 0.142 -> 0.134 ms).  sbox_lat: the branch-free multiply
-// (14 VALU), straight-line code; the quad form keeps it (with the branch form its k_phase1 went
-// 1.93 -> 2.03 ms, profiles/r04u_sbox_lat_branch.txt).
+// branch per stage (x^2; x^3 and x^4; x^7), as the throughput S-box (sbox_n).  It was the S-box of
+// the retired DPP row permutation (DESIGN.md "Retired build options"); p2v_selftest op 7 is now
+// its only user.
 __host__ __device__ __forceinline__ uint64_t sbox_lat(uint64_t x) {
 #if defined(__HIP_DEVICE_COMPILE__)
   const uint64_t x2 = gl::mul_nc_dev(x, x), x3 = gl::mul_nc_dev(x, x2), x4 = gl::mul_nc_dev(x2, x2);
@@ -154,16 +145,7 @@ __host__ __device__ __forceinline__ void partial_round(uint64_t s[12], int r) {
 
 #if defined(__HIPCC__)
 // ---------------------------------------------------------------- device permutation
-// Same function, restructured for the gfx950 VALU (one permutation per lane):
-//  * the round constant of round r+1 is folded into round r's MDS: each row's two 32-bit-half
-//    accumulators START at the constant's halves (the first v_mad_u64_u32's addend), so
-//    rounds 1..29 spend no instruction on constant addition;
-//  * every MDS multiply-add is an explicit v_mad_u64_u32 with the matrix entry as an inline
-//    constant (the compiler otherwise turns 2/16 into 64-bit shifts of zero-extended register
-//    pairs and pays a v_mov per pair);
-//  * rounds alternate between two register sets (s -> t -> s), so no copies are needed at
-//    loop edges; full rounds run as 4 pairs, the 22 partial rounds as merged blocks (PBlock,
-//    P2V_PMERGE; 11 pairs of single rounds with P2V_PMERGE=0).
+// Constant tables of the device form (its structure is described at permute_dev below).
 struct RcSplit { uint64_t lo[31 * 12], hi[31 * 12]; };   // round 30 = 0 (after the last MDS)
 __host__ __device__ constexpr RcSplit make_rc_split() {
   RcSplit t{};
@@ -186,10 +168,8 @@ __host__ __device__ constexpr ZhConst make_zh() {
 }
 static __constant__ RcSplit c_rc_split = make_rc_split();
 static __constant__ ZhConst c_zh = make_zh();
-#ifndef P2V_ZH_FOLD
-#define P2V_ZH_FOLD 1   // round 0 of a zh permutation peeled before the round loop, its constant columns folded (below)
-#endif
-// Round 0 of a permutation whose words 8..11 enter as 0 (2-to-1 compression, first sponge block):
+// Round 0 of a permutation whose words 8..11 enter as 0 (2-to-1 compression, first sponge block) is
+// peeled before the round loop with its constant columns folded:
 // their S-box outputs z_j are constants (c_zh), so row i of that round's MDS plus round 1's constant
 // is sum_{j<8} M_ij y_j + K_i with K_i = rc[1][i] + sum_{j>=8} M_ij z_j (mod p), whose 32-bit halves
 // start the row's accumulators: 8 MADs per row less (96 per permutation).  Same field elements as
@@ -229,19 +209,10 @@ struct PBlock {
   uint32_t cf[14][16];      // rows: chain k = 2, 3 at [k - 2], output row i at [2 + i]; G coefs [0..11], H (m = 2..D-1) at [12 + m - 2]
   uint64_t dlo[16], dhi[16];  // halves of d: chain k = 1..D-1 at [k - 1], output row i at [4 + i]
 };
-#ifndef P2V_PMERGE
-#define P2V_PMERGE 4   // partial rounds per block: 4 (blocks 4,4,4,4,4,2), 3 (3 x 7 + 1), 2 (2 x 11), 0 (one MDS per round)
-#endif
-#if P2V_PMERGE == 4
+// partial rounds per block (the schedules 3 x 7 + 1, 2 x 11 and one MDS per round are retired:
+// DESIGN.md "Retired build options")
 static constexpr int PM_NB = 6;
 static constexpr int PM_SCHED[PM_NB] = {4, 4, 4, 4, 4, 2};
-#elif P2V_PMERGE == 3
-static constexpr int PM_NB = 8;
-static constexpr int PM_SCHED[PM_NB] = {3, 3, 3, 3, 3, 3, 3, 1};
-#else
-static constexpr int PM_NB = 11;
-static constexpr int PM_SCHED[PM_NB] = {2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2};
-#endif
 struct PMTab { PBlock b[PM_NB]; };
 __host__ __device__ constexpr uint64_t cx_addp(uint64_t a, uint64_t b) { return (uint64_t)(((unsigned __int128)a + b) % gl::P); }
 __host__ __device__ constexpr uint64_t cx_mulp(uint64_t a, uint64_t b) { return (uint64_t)(((unsigned __int128)a * b) % gl::P); }
@@ -319,29 +290,15 @@ namespace dv {
 // into 64-bit shifts of zero-extended register pairs).  The pair must lie inside the kernel's
 // SGPR budget: a build that forces a higher occupancy (e.g. amdgpu_waves_per_eu(7) on k_merkle)
 // makes hipcc warn "clobber list contains reserved registers: s94, s95", and is not valid.
-#ifndef P2V_MADK_C
-#define P2V_MADK_C 0   // 1: MDS MADs in plain C (measured slower, round 5: below)
-#endif
-// P2V_MADK_C = 1 writes the MDS MADs as plain C (a * C + acc, C an inline constant; powers of two
-// stay asm, the compiler would turn them into 64-bit shifts and masks), so that no s_nop pads them
-// as it pads every inline-asm statement with an SGPR output (k_merkle: 2 855 -> 2 219 static
-// s_nop).  Measured (profiles/r05c_madk.txt): the isolated permutation 3.22 -> 2.69 G perm/s
-// (generic) and 3.35 -> 2.71-2.80 (compression), the quick line 1.10 M: the compiler's schedule of
-// the plain MADs (more moves and 64-bit adds) costs far more than the padding.  Kept for the record.
+// (The plain-C form of these MADs measured slower: DESIGN.md "Retired build options".)
 template <uint32_t C>
 __device__ __forceinline__ uint64_t madk(uint32_t a, uint64_t acc) {
-#if P2V_MADK_C
-  if constexpr ((C & (C - 1)) != 0) return (uint64_t)a * C + acc;
-#endif
   uint64_t d;
   asm("v_mad_u64_u32 %0, s[94:95], %1, %2, %3" : "=v"(d) : "v"(a), "n"(C), "v"(acc) : "s94", "s95");
   return d;
 }
 template <uint32_t C>
 __device__ __forceinline__ uint64_t madk_s(uint32_t a, uint64_t acc) {   // acc wave-uniform (SGPR pair)
-#if P2V_MADK_C
-  if constexpr ((C & (C - 1)) != 0) return (uint64_t)a * C + acc;
-#endif
   uint64_t d;
   asm("v_mad_u64_u32 %0, s[94:95], %1, %2, %3" : "=v"(d) : "v"(a), "n"(C), "s"(acc) : "s94", "s95");
   return d;
@@ -354,15 +311,11 @@ __device__ __forceinline__ uint64_t reduce_rows(uint64_t al, uint64_t ah) {
   uint64_t c1, c2;
   const uint64_t t = madm1_co((uint32_t)(ah >> 32), al, c1);   // < 2^45: no carry
   const uint32_t rh = add_co((uint32_t)(t >> 32), (uint32_t)ah, c1);
-#if P2V_MDS_BRANCH
   // t >> 32 < 2^11, so the carry needs ah_lo > 2^32 - 2^11: ~2^-21 per row for data that is
   // not chosen to hit it.  A wave-uniform branch around the fix-up: 2 VALU per row less.
   uint64_t r = ((uint64_t)rh << 32) | (uint32_t)t;
   if (__builtin_expect(c1 != 0, 0)) r = madm1_co(mask_1(c1), r, c2);
   return r;
-#else
-  return madm1_co(mask_1(c1), ((uint64_t)rh << 32) | (uint32_t)t, c2);
-#endif
 }
 template <int I, int J, int E = 12>
 __device__ __forceinline__ void mds_acc(const uint64_t* s, uint64_t& al, uint64_t& ah) {
@@ -373,7 +326,6 @@ __device__ __forceinline__ void mds_acc(const uint64_t* s, uint64_t& al, uint64_
     mds_acc<I, J + 1, E>(s, al, ah);
   }
 }
-#if P2V_MDS_BRANCH == 2
 // one row before its (rare) fix-up: r = t + ah_lo 2^32 with the carry-out mask c.  NW = 8: the
 // row over words 0..7 only (the peeled round 0 of a zh permutation: words 8..11 folded into k)
 template <int I, int NW = 12>
@@ -406,16 +358,9 @@ __device__ __forceinline__ void mds_group(const uint64_t* s, uint64_t* t, const 
   }
   t[I] = r0; t[I + 1] = r1; t[I + 2] = r2; t[I + 3] = r3;
 }
-#endif
 // t[I..E) = (M s)[I..E) + k (k = the next round's constants, split into halves)
 template <int I, int E>
 __device__ __forceinline__ void mds_rows(const uint64_t* s, uint64_t* t, const uint64_t* kl, const uint64_t* kh) {
-#if P2V_POSEIDON_ASMBLK
-  if constexpr (I < E) {
-    t[I] = p2asm::mds_row<I>(s, kl[I], kh[I]);
-    mds_rows<I + 1, E>(s, t, kl, kh);
-  }
-#else
   if constexpr (I < E) {
     constexpr uint32_t C = mds_coeff(I, 0);
     uint64_t al = madk_s<C>((uint32_t)s[0], kl[I]);
@@ -424,15 +369,6 @@ __device__ __forceinline__ void mds_rows(const uint64_t* s, uint64_t* t, const u
     t[I] = reduce_rows(al, ah);
     mds_rows<I + 1, E>(s, t, kl, kh);
   }
-#endif
-}
-__device__ __forceinline__ uint64_t sbox_dev(uint64_t x) {
-#if P2V_POSEIDON_ASMBLK
-  const uint64_t x2 = p2asm::mul_blk(x, x), x3 = p2asm::mul_blk(x, x2), x4 = p2asm::mul_blk(x2, x2);
-  return p2asm::mul_blk(x3, x4);
-#else
-  return sbox(x);
-#endif
 }
 // N independent S-boxes x -> x^7 in place, their products interleaved: each stage (x^2; x^3 and
 // x^4; x^7) is one basic block of 1-2 N independent multiplies, and the rare -2^64 fix-up of
@@ -470,61 +406,38 @@ __device__ __forceinline__ void sbox_n(uint64_t* x) {
     for (int i = 0; i < N; i++) x[i] = gl::mul_fix_neg(x[i], n2[i]);
   }
 }
-#ifndef P2V_SBOX_ILP
-#define P2V_SBOX_ILP 2   // S-boxes per interleaved group in the full rounds (sbox_n); 0: one p2::sbox per word
-#endif
+static constexpr int SBOX_ILP = 2;   // S-boxes per interleaved group in the full rounds (sbox_n)
 // the S-boxes of words [I, E) of a full round
 template <int I, int E>
 __device__ __forceinline__ void sbox_range(uint64_t* s) {
-#if P2V_SBOX_ILP > 0
   if constexpr (I < E) {
-    constexpr int K = (E - I) < P2V_SBOX_ILP ? (E - I) : P2V_SBOX_ILP;
+    constexpr int K = (E - I) < SBOX_ILP ? (E - I) : SBOX_ILP;
     sbox_n<K>(s + I);
     sbox_range<I + K, E>(s);
   }
-#else
-#pragma unroll
-  for (int i = I; i < E; i++) s[i] = sbox_dev(s[i]);
-#endif
 }
 __device__ __forceinline__ uint64_t sbox_one(uint64_t x) {
-#if P2V_SBOX_ILP > 0
   sbox_n<1>(&x);
   return x;
-#else
-  return sbox_dev(x);
-#endif
 }
-// round r: s -> t (s is clobbered by the S-boxes); t = M sbox(s) + rc[r + 1].
+// full round r: s -> t (s is clobbered by the S-boxes); t = M sbox(s) + rc[r + 1].
 // zh0: round 0 with state words 8..11 entering as 0 (their S-box outputs are constants).
 // g: which groups of 4 output rows are needed (bit k = rows 4k..4k+3); wave-uniform.
-template <bool FULL>
 __device__ __forceinline__ void round_pp(uint64_t* s, uint64_t* t, int r, bool zh0, int g) {
-  if (FULL) {
-    sbox_range<0, 8>(s);
-    if (zh0) {
+  sbox_range<0, 8>(s);
+  if (zh0) {
 #pragma unroll
-      for (int i = 8; i < 12; i++) s[i] = c_zh.z[i - 8];
-    } else {
-      sbox_range<8, 12>(s);
-    }
+    for (int i = 8; i < 12; i++) s[i] = c_zh.z[i - 8];
   } else {
-    s[0] = sbox_one(s[0]);
+    sbox_range<8, 12>(s);
   }
   const uint64_t* kl = c_rc_split.lo + 12 * (r + 1);
   const uint64_t* kh = c_rc_split.hi + 12 * (r + 1);
-#if P2V_MDS_BRANCH == 2
   if (g & 1) mds_group<0>(s, t, kl, kh);
   if (g & 2) mds_group<4>(s, t, kl, kh);
   if (g & 4) mds_group<8>(s, t, kl, kh);
-#else
-  if (g & 1) mds_rows<0, 4>(s, t, kl, kh);
-  if (g & 2) mds_rows<4, 8>(s, t, kl, kh);
-  if (g & 4) mds_rows<8, 12>(s, t, kl, kh);
-#endif
 }
 
-#if P2V_MDS_BRANCH == 2 && P2V_ZH_FOLD
 // the peeled round 0 of a zh permutation: s -> t = M sbox(s) + rc[1] with s[8..11] = 0 + rc[0][8..11]
 // never formed (their S-boxes and MDS columns are c_zrc); s[0..7] already hold + rc[0]
 __device__ __forceinline__ void round0_zh(uint64_t* s, uint64_t* t) {
@@ -533,7 +446,6 @@ __device__ __forceinline__ void round0_zh(uint64_t* s, uint64_t* t) {
   mds_group<4, 8>(s, t, c_zrc.lo, c_zrc.hi);
   mds_group<8, 8>(s, t, c_zrc.lo, c_zrc.hi);
 }
-#endif
 
 // ---- merged partial rounds (see PBlock): coefficients are wave-uniform table entries (SGPR
 // operands; gfx950 VOP3 takes no literal, and one SGPR per instruction, so the row's first
@@ -544,7 +456,7 @@ __device__ __forceinline__ uint64_t madv(uint32_t a, uint32_t c, uint64_t acc) {
   asm("v_mad_u64_u32 %0, s[94:95], %1, %2, %3" : "=v"(d) : "v"(a), "s"(c), "v"(acc) : "s94", "s95");
   return d;
 }
-// al + 2^32 ah for row sums < 2^24 (D <= 3): as reduce_rows, the carry fix-up without a branch
+// al + 2^32 ah for row sums < 2^24 (chain depth <= 3): as reduce_rows, the carry fix-up without a branch
 __device__ __forceinline__ uint64_t reduce_t(uint64_t al, uint64_t ah) {
   using namespace gl::ax;
   uint64_t c0, c1, c2;
@@ -579,16 +491,16 @@ __device__ __forceinline__ void prow(const uint64_t* s, const uint64_t* yh, uint
     ah = madv((uint32_t)(yh[m] >> 32), cf[12 + m], ah);
   }
 }
-template <int D, int I>
-__device__ __forceinline__ void pblock_rows(const uint64_t* s, const uint64_t* y, uint64_t* t, const PBlock& B) {
+// D = 4 output rows I..11
+template <int I>
+__device__ __forceinline__ void pblock4_rows(const uint64_t* s, const uint64_t* y, uint64_t* t, const PBlock& B) {
   if constexpr (I < 12) {
     uint64_t al, ah;
-    prow<mds_coeff(I, 0), D - 2>(s, y + 2, y[D], B.cf[2 + I], B.dlo[4 + I], B.dhi[4 + I], al, ah);
-    t[I] = D == 4 ? reduce_w(al, ah) : reduce_t(al, ah);
-    pblock_rows<D, I + 1>(s, y, t, B);
+    prow<mds_coeff(I, 0), 2>(s, y + 2, y[4], B.cf[2 + I], B.dlo[4 + I], B.dhi[4 + I], al, ah);
+    t[I] = reduce_w(al, ah);
+    pblock4_rows<I + 1>(s, y, t, B);
   }
 }
-#if P2V_MDS_BRANCH == 2
 // D = 2 output row before its (rare: ~2^-15) carry fix-up, as row_unfixed
 template <int I>
 __device__ __forceinline__ void prow2_unfixed(const uint64_t* s, uint64_t y2, const PBlock& B, uint64_t& r, uint64_t& c) {
@@ -615,11 +527,11 @@ __device__ __forceinline__ void pblock2_group(const uint64_t* s, uint64_t y2, ui
   }
   t[I] = r0; t[I + 1] = r1; t[I + 2] = r2; t[I + 3] = r3;
 }
-#endif
-// D partial rounds: s = the state entering the block's first round (its constants included),
+// D = 2 or 4 partial rounds: s = the state entering the block's first round (its constants included),
 // t = the state entering the round after the block.  s is clobbered.
 template <int D>
 __device__ __forceinline__ void pblock(uint64_t* s, uint64_t* t, const PBlock& B) {
+  static_assert(D == 2 || D == 4, "PM_SCHED holds blocks of 4 and 2");
   uint64_t y[D + 1];
   s[0] = sbox_one(s[0]);   // y1, word 0 of s'
   {   // chain row 1 (row 0 of M s' + d1): inline MDS entries
@@ -628,25 +540,19 @@ __device__ __forceinline__ void pblock(uint64_t* s, uint64_t* t, const PBlock& B
     mds_acc<0, 1>(s, al, ah);
     y[2] = sbox_one(reduce_rows(al, ah));
   }
-  if constexpr (D >= 3) {   // chain row 2: row sums < 2^16, the branch form of the fix-up
-    uint64_t al, ah;
+  if constexpr (D == 4) {
+    uint64_t al, ah;   // chain row 2: row sums < 2^16, the branch form of the fix-up
     prow<mds_coeff(0, 0), 0>(s, nullptr, y[2], B.cf[0], B.dlo[1], B.dhi[1], al, ah);
     y[3] = sbox_one(reduce_rows(al, ah));
-  }
-  if constexpr (D >= 4) {   // chain row 3: row sums < 2^24
-    uint64_t al, ah;
+    // chain row 3: row sums < 2^24
     prow<mds_coeff(0, 0), 1>(s, y + 2, y[3], B.cf[1], B.dlo[2], B.dhi[2], al, ah);
     y[4] = sbox_one(reduce_t(al, ah));
-  }
-#if P2V_MDS_BRANCH == 2
-  if constexpr (D == 2) {
+    pblock4_rows<0>(s, y, t, B);
+  } else {
     pblock2_group<0>(s, y[2], t, B);
     pblock2_group<4>(s, y[2], t, B);
     pblock2_group<8>(s, y[2], t, B);
-    return;
   }
-#endif
-  pblock_rows<D, 0>(s, y, t, B);
 }
 }  // namespace dv
 
@@ -658,11 +564,12 @@ __device__ __forceinline__ void pblock(uint64_t* s, uint64_t* t, const PBlock& B
 //    accumulators START at the constant's halves (the first v_mad_u64_u32's addend), so
 //    rounds 1..29 spend no instruction on constant addition;
 //  * every MDS multiply-add is an explicit v_mad_u64_u32 with the matrix entry as an inline
-//    constant;
+//    constant (the compiler otherwise turns 2/16 into 64-bit shifts of zero-extended register
+//    pairs and pays a v_mov per pair);
 //  * rounds alternate between two register sets (s -> t -> s), so no copies are needed at
 //    loop edges; full rounds run as 4 pairs, the 22 partial rounds as merged blocks (PBlock,
-//    P2V_PMERGE; 11 pairs of single rounds with P2V_PMERGE=0).
-// FOLD: compile the peeled zh round 0 (P2V_ZH_FOLD) into this call site; false leaves it out where zh
+//    PM_SCHED).
+// FOLD: compile the peeled zh round 0 (round0_zh) into this call site; false leaves it out where zh
 // is never set (the leaf sponge's second block of a trip: with both of its call sites folded,
 // k_phase1 spilled 8 B)
 template <bool FOLD = true>
@@ -682,15 +589,13 @@ __device__ __forceinline__ void permute_dev(uint64_t s[12], bool zh = false, int
 #pragma unroll
   for (int i = 0; i < 8; i++) s[i] = add_nc(s[i], rc0[i]);
   int k0 = 0;
-#if P2V_MDS_BRANCH == 2 && P2V_ZH_FOLD
   // zh: rounds 0 and 1 peeled before the loop, round 0 over words 0..7 only (c_zrc); the loop body
   // stays the one generic full-round pair (a second round-0 form inside it spilled, round 5)
   if constexpr (FOLD) if (zh) {
     dv::round0_zh(s, t);
-    dv::round_pp<true>(t, s, 1, false, 7);
+    dv::round_pp(t, s, 1, false, 7);
     k0 = 1;
   }
-#endif
   if (!zh) {
 #pragma unroll
     for (int i = 8; i < 12; i++) s[i] = add_nc(s[i], rc0[i]);
@@ -698,10 +603,9 @@ __device__ __forceinline__ void permute_dev(uint64_t s[12], bool zh = false, int
 #pragma unroll 1
   for (int k = k0; k < 4; k++) {   // full-round pairs (0,1) (2,3) (26,27) (28,29)
     const int r = k < 2 ? 2 * k : 22 + 2 * k;
-    dv::round_pp<true>(s, t, r, zh && k == 0, 7);   // (k == 0 with zh: only when not peeled)
-    dv::round_pp<true>(t, s, r + 1, false, k == 3 ? gm : 7);
+    dv::round_pp(s, t, r, zh && k == 0, 7);   // (k == 0 with zh: only when not peeled)
+    dv::round_pp(t, s, r + 1, false, k == 3 ? gm : 7);
     if (k == 1) {
-#if P2V_PMERGE == 4
       // blocks of 4, 4, 4, 4, 4, 2 merged partial rounds; each loop trip reads its own table
       // copies, so the coefficient loads stay inside the loop (no SGPR spills)
 #pragma unroll 1
@@ -711,29 +615,6 @@ __device__ __forceinline__ void permute_dev(uint64_t s[12], bool zh = false, int
       }
       dv::pblock<4>(s, t, c_pm.b[4]);
       dv::pblock<2>(t, s, c_pm.b[5]);
-#elif P2V_PMERGE == 3
-#pragma unroll 1
-      for (int b = 0; b < 6; b += 2) {
-        dv::pblock<3>(s, t, c_pm.b[b]);
-        dv::pblock<3>(t, s, c_pm.b[b + 1]);
-      }
-      dv::pblock<3>(s, t, c_pm.b[6]);
-      dv::round_pp<false>(t, s, 25, false, 7);
-#elif P2V_PMERGE == 2
-#pragma unroll 1
-      for (int b = 0; b < 10; b += 2) {
-        dv::pblock<2>(s, t, c_pm.b[b]);
-        dv::pblock<2>(t, s, c_pm.b[b + 1]);
-      }
-      dv::round_pp<false>(s, t, 24, false, 7);
-      dv::round_pp<false>(t, s, 25, false, 7);
-#else
-#pragma unroll 1
-      for (int q = 4; q < 26; q += 2) {   // partial-round pairs
-        dv::round_pp<false>(s, t, q, false, 7);
-        dv::round_pp<false>(t, s, q + 1, false, 7);
-      }
-#endif
     }
   }
   // canonical outputs for the groups the caller reads (the others are undefined: their last MDS

@@ -16,14 +16,11 @@
 
 namespace qp {
 
-#ifndef P2V_QUAD_SBOX
-#define P2V_QUAD_SBOX 1
-#endif
 // The chain's S-box (latency-bound waves: an instruction's cost is its issue slot, s_nop padding
-// included): 1 = the asm-block multiply of lposeidon.h (one statement, one padding per multiply,
-// round 5), 0 = p2::sbox_lat (the branch-free multiply, five asm statements per multiply)
+// included): the asm-block multiply of lposeidon.h (one statement, one padding per multiply,
+// round 5; p2::sbox_lat, five asm statements per multiply, in the host pass only)
 __device__ __forceinline__ uint64_t sbox_q(uint64_t x) {
-#if P2V_QUAD_SBOX && defined(__HIP_DEVICE_COMPILE__)
+#if defined(__HIP_DEVICE_COMPILE__)
   return lp::sbox(x);
 #else
   return p2::sbox_lat(x);
@@ -128,9 +125,7 @@ __host__ __device__ constexpr QMTab make_qm() {
   }
   return T;
 }
-#if P2V_PMERGE
 static __constant__ QMTab c_qm = make_qm();
-#endif
 
 // The permutation's per-lane tables, copied into LDS once per transcript workgroup (tlds_fill).
 // A serial chain cannot afford a vector-memory wait inside the permutation: vmcnt retires in
@@ -149,17 +144,13 @@ __device__ __forceinline__ void tlds_fill(TLds& T, int tid, int n) {
   uint64_t* rd = (uint64_t*)&T.rc;
   for (int i = tid; i < (int)(sizeof(p2::RcSplit) / 8); i += n) rd[i] = rs[i];
   if (tid < 12) T.rc0[tid] = p2::c_round_constants[tid];
-#if P2V_PMERGE
   const uint64_t* qs = (const uint64_t*)&c_qm;
   uint64_t* qd = (uint64_t*)T.qb;
   for (int i = tid; i < (int)(sizeof(QMTab) / 8); i += n) qd[i] = qs[i];
-#endif
   __syncthreads();
 }
 
-#if P2V_PMERGE && defined(__HIP_DEVICE_COMPILE__)
-#define P2V_QMERGE 1
-
+#if defined(__HIP_DEVICE_COMPILE__)
 // acc + a c, c a per-lane VGPR coefficient
 __device__ __forceinline__ uint64_t madl(uint32_t a, uint32_t c, uint64_t acc) {
   return (uint64_t)a * c + acc;
@@ -182,27 +173,13 @@ __device__ __forceinline__ void chain_part(const uint64_t (&X)[4][3], const p2::
 }
 // The chain's S-boxes (inputs the same in all four lanes of the quad): x^3 on lanes 0, 2 and x^4 on
 // lanes 1, 3, swapped and multiplied (lp::sbox_u, round 6): three multiplies per lane instead of
-// four, bit-identical (P2V_QUAD_SBOX2=0: sbox_q)
-#ifndef P2V_QUAD_SBOX2
-#define P2V_QUAD_SBOX2 1
-#endif
-__device__ __forceinline__ uint64_t sbox_qu(uint64_t x, int t) {
-#if P2V_QUAD_SBOX2 && P2V_QUAD_SBOX
-  return lp::sbox_u(x, t);
-#else
-  (void)t;
-  return sbox_q(x);
-#endif
-}
+// four, bit-identical to sbox_q
+__device__ __forceinline__ uint64_t sbox_qu(uint64_t x, int t) { return lp::sbox_u(x, t); }
 template <int D>
 __device__ __forceinline__ void qblock(uint64_t x[3], int t, const p2::PBlock& B, const QBlock& Q) {
   // y1 = sbox(word 0) from lane 0; s' = the state with y1 in word 0
   uint64_t y[D + 1];
-#if P2V_QUAD_SBOX2 && P2V_QUAD_SBOX
   y[1] = sbox_qu(bcast64(x[0], 0), t);
-#else
-  y[1] = bcast64(sbox_q(x[0]), 0);
-#endif
   x[0] = t == 0 ? y[1] : x[0];
   uint64_t X[4][3];
 #pragma unroll
@@ -257,56 +234,25 @@ __device__ __forceinline__ void qblock(uint64_t x[3], int t, const p2::PBlock& B
     x[m] = D == 4 ? p2::dv::reduce_w(al, ah) : p2::dv::reduce_t(al, ah);
   }
 }
-#endif
 
-// the quad's permutation; x = this lane's three words (inputs < 2^64, outputs canonical).
-// Partial rounds take the S-box off the critical path: the MDS runs on the state with word 0
-// zeroed while lane 0's S-box chain is in flight, then sbox(word 0), broadcast from lane 0,
-// is added with column 0 of M (M[3t+m][0], per lane).
+// the quad's permutation; x = this lane's three words (inputs < 2^64, outputs canonical): full
+// rounds 0..3, the merged partial-round blocks (qblock), full rounds 26..29
 __device__ __forceinline__ void permute(uint64_t x[3], int t, const TLds& T) {
   {
     const uint64_t* R = T.rc0 + 3 * t;
 #pragma unroll
     for (int k = 0; k < 3; k++) x[k] = p2::add_nc(x[k], R[k]);
   }
-  // M[i][0] = circ[(12 - i) % 12] (+ 8 for i = 0), rows i = 3t .. 3t+2 (Hash/Constants.hs:19-25)
-  const uint32_t col0[3] = {t == 0 ? 25u : t == 1 ? 18u : t == 2 ? 13u : 16u,
-                            t == 0 ? 20u : t == 1 ? 39u : t == 2 ? 28u : 41u,
-                            t == 0 ? 34u : t == 1 ? 13u : t == 2 ? 2u : 15u};
   uint64_t kl[3], kh[3], nkl[3], nkh[3];
-#if P2V_QMERGE
-  // full rounds 0..3, the merged partial-round blocks, full rounds 26..29
   lane_rc(T.rc, 1, t, nkl, nkh);
 #pragma unroll 1
   for (int r = 0; r < 8; r++) {
     if (r == 4) {
-#if P2V_PMERGE == 4
 #pragma unroll 1
       for (int b = 0; b < 5; b++) qblock<4>(x, t, p2::c_pm.b[b], T.qb[b]);
       qblock<2>(x, t, p2::c_pm.b[5], T.qb[5]);
-#elif P2V_PMERGE == 3
-#pragma unroll 1
-      for (int b = 0; b < 7; b++) qblock<3>(x, t, p2::c_pm.b[b], T.qb[b]);
-#else
-#pragma unroll 1
-      for (int b = 0; b < 11; b++) qblock<2>(x, t, p2::c_pm.b[b], T.qb[b]);
-#endif
       lane_rc(T.rc, 27, t, nkl, nkh);
     }
-#if P2V_PMERGE == 3
-    if (r == 4) {   // the schedule's single plain partial round (25)
-      lane_rc(T.rc, 26, t, kl, kh);
-      const uint64_t w0 = x[0];
-      x[0] = t == 0 ? 0 : w0;
-      uint64_t al[3], ah[3];
-      mds_acc(x, t, kl, kh, al, ah);
-      const uint64_t sb = bcast64(sbox_q(w0), 0);
-#pragma unroll
-      for (int m = 0; m < 3; m++) { al[m] += (uint64_t)(uint32_t)sb * col0[m]; ah[m] += (sb >> 32) * col0[m]; }
-#pragma unroll
-      for (int m = 0; m < 3; m++) x[m] = p2::mds_reduce(al[m], ah[m]);
-    }
-#endif
     const int rr = r < 4 ? r : r + 22;   // 0..3, 26..29
 #pragma unroll
     for (int k = 0; k < 3; k++) { kl[k] = nkl[k]; kh[k] = nkh[k]; }
@@ -318,37 +264,12 @@ __device__ __forceinline__ void permute(uint64_t x[3], int t, const TLds& T) {
 #pragma unroll
     for (int m = 0; m < 3; m++) x[m] = p2::mds_reduce(al[m], ah[m]);
   }
-  (void)col0;
-#else
-  lane_rc(T.rc, 1, t, nkl, nkh);
-#pragma unroll 1
-  for (int r = 0; r < 30; r++) {
-#pragma unroll
-    for (int k = 0; k < 3; k++) { kl[k] = nkl[k]; kh[k] = nkh[k]; }
-    lane_rc(T.rc, r + 2 <= 30 ? r + 2 : 30, t, nkl, nkh);   // row 30 of the split table is zero
-    uint64_t al[3], ah[3];
-    if (r < 4 || r >= 26) {
-#pragma unroll
-      for (int k = 0; k < 3; k++) x[k] = sbox_q(x[k]);
-      mds_acc(x, t, kl, kh, al, ah);
-    } else {
-      const uint64_t w0 = x[0];
-      x[0] = t == 0 ? 0 : w0;
-      mds_acc(x, t, kl, kh, al, ah);           // independent of the S-box below
-      const uint64_t s = bcast64(sbox_q(w0), 0);
-#pragma unroll
-      for (int m = 0; m < 3; m++) {
-        al[m] += (uint64_t)(uint32_t)s * col0[m];
-        ah[m] += (s >> 32) * col0[m];
-      }
-    }
-#pragma unroll
-    for (int m = 0; m < 3; m++) x[m] = p2::mds_reduce(al[m], ah[m]);
-  }
-#endif
 #pragma unroll
   for (int k = 0; k < 3; k++) x[k] = gl::canon(x[k]);
 }
+#elif defined(__HIPCC__)
+__device__ void permute(uint64_t x[3], int t, const TLds& T);   // device-only
+#endif
 
 // word `pos` (uniform, 0..11) of the quad's state, broadcast to all four lanes
 __device__ __forceinline__ uint64_t get_word(const uint64_t x[3], int pos) {

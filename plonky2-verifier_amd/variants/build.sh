@@ -1,7 +1,7 @@
 #!/bin/bash
 # Measurement / isolation builds of libp2v with extra compile flags, loaded through P2V_LIB:
 #   variants/build.sh <name> "<flags>"   ->   variants/libp2v_<name>.so
-#   pm:    -DP2V_PROOF_MAJOR=1   (kernels read the proof-major batch in place, no k_transpose)
+#   w7:    -DP2V_MERKLE_WAVES=7   (k_merkle at a forced 7 waves per SIMD)
 set -e
 cd "$(dirname "$0")/.."
 NAME=$1; EXTRA=$2

@@ -1211,7 +1211,7 @@ def _mds_fixup_cases(rng, n=512):
 
 
 def test_gpu_mds_layer_carry_fixup(p2v):
-    """the grouped MDS carry fix-up (P2V_MDS_BRANCH 2) is reached deterministically:
+    """the grouped MDS carry fix-up (poseidon.h mds_group) is reached deterministically:
     crafted states fire it in 1-3 rows of a group and leave the group's other rows alone (and
     near-misses just below the threshold); p2v_selftest op 4 runs one MDS layer exactly as the
     permutation does, compared with exact integer arithmetic."""

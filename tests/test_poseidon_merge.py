@@ -21,7 +21,7 @@ M = [[CIRC[(j - i) % 12] + (8 if i == j == 0 else 0) for j in range(12)] for i i
 KAT = [0xd64e1e3efc5b8e9e, 0x53666633020aaa47, 0xd40285597c6a8825, 0x613a4f81e81231d2,
        0x414754bfebd051f0, 0xcb1f8980294a023f, 0x6eb2a9e4d54a9d0f, 0x1902bc3af467e056,
        0xf045d5eafdc6021f, 0xe4150f77caaa3be5, 0xc9bfd01d39b50cce, 0x5c0a27fcb0e1459b]
-SCHEDULES = {4: [4, 4, 4, 4, 4, 2], 3: [3] * 7 + [1], 2: [2] * 11}   # P2V_PMERGE -> PM_SCHED
+SCHEDULES = {4: [4, 4, 4, 4, 4, 2], 3: [3] * 7 + [1], 2: [2] * 11}   # block depth -> schedule; poseidon.h PM_SCHED is the depth-4 one
 
 
 def _round_constants():

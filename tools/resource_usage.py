@@ -2,7 +2,7 @@
 """Per-kernel register / scratch / occupancy table of the libp2v device code, from the
 compiler's kernel-resource-usage remarks (no GPU needed).
 
-usage: tools/resource_usage.py [-D...]...   (extra hipcc flags, e.g. -DP2V_MUL_PRODUCT=0)
+usage: tools/resource_usage.py [-D...]...   (extra hipcc flags, e.g. -DP2V_MERKLE_WAVES=5)
 """
 import concurrent.futures as cf
 import os
