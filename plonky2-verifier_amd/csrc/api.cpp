@@ -23,7 +23,6 @@ extern "C" __global__ void k_phase1_pair(DevCircuit, int, int);
 extern "C" __global__ void k_transcript(DevCircuit, int);
 extern "C" __global__ void k_transcript_lane(DevCircuit, int);
 extern "C" __global__ void k_transcript_pair(DevCircuit, int);
-extern "C" __global__ void k_transcript_x(DevCircuit, int);
 extern "C" __global__ void k_leaf(DevCircuit);
 extern "C" __global__ void k_merkle(DevCircuit);
 extern "C" __global__ void k_merkle_row(DevCircuit);
@@ -58,7 +57,7 @@ thread_local std::string g_err;
 int fail(int code, const std::string& msg) { g_err = msg; return code; }
 
 // per-kernel timing slots; k_fri and k_vanish run on the side stream, concurrently with k_merkle
-// (k_leaf + k_transcript: the split form of k_phase1, env P2V_PHASE1=split, measurement only).
+// (k_leaf + k_transcript: the two halves of k_phase1 as the lookahead path launches them).
 // Slot 0 is the retired transposing build's; it keeps its name and place (callers index by this
 // list) and is never recorded.
 const char* kKernelNames = "k_transpose,k_phase1,k_merkle,k_fri,k_vanish,k_status,k_vanish_final,k_lut,k_leaf,k_transcript";
@@ -136,7 +135,7 @@ struct p2v_verifier {
   DevBuf m_plan, m_fol, m_chain, m_count, m_fix, m_badq, m_node;   // shared-node Merkle paths (dev.h mcse)
   DevBuf t_cs, t_kis, t_gkind, t_gpar, t_ggrp, t_gwoff, t_w, t_gs, t_ge, t_lin, t_lout, t_loff, t_llen, t_tw, t_ops, t_vit, t_rin, t_rout, t_roff, t_rch, t_pbase, t_pw;
   hipEvent_t ev[2 * kNumKernels];   // start/end per kernel
-  hipEvent_t dep_p1 = nullptr, dep_side = nullptr, dep_tr = nullptr;
+  hipEvent_t dep_p1 = nullptr, dep_side = nullptr;
   hipEvent_t p1_done = nullptr;      // recorded on the caller's stream after phase 1 (p2v_verifier_chain)
   std::atomic<bool> p1_recorded{false};   // read by the workspaces chained to this one, from their host threads
   p2v_verifier* chain_prev = nullptr;     // chain links: guarded by g_chain_mu
@@ -155,7 +154,6 @@ struct p2v_verifier {
   unsigned la_seq = 0;
   float last_ms[kNumKernels] = {0};
   bool timed = false;
-  bool fri_first = false;           // side stream order: k_fri before the vanishing kernels (env P2V_FRI_FIRST=1)
   int transcript_mode = 0;          // 0 auto, 1 row, 2 quad, 3 lane, 4 pair (env P2V_TRANSCRIPT)
   int quad_min_batch = 4096;        // auto: quad form from this batch size on (env P2V_QUAD_MIN); round 5: with the
                                     // latency row form (lposeidon.h) the row transcript wins up to 2048 proofs
@@ -167,13 +165,6 @@ struct p2v_verifier {
   int lat_max_batch = 64;           // latency mode (row-form Merkle paths, k_fri on its own stream) up to this
                                     // batch size (env P2V_LAT_MAX, measurement)
   bool single_stream = false;       // env P2V_SINGLE_STREAM=1: no side stream (measurement)
-  int side_prio = 0;                // env P2V_SIDE_PRIO=1: side stream at the device's highest priority (measured: no effect)
-  int side_wg = 256;                // env P2V_SIDE_WG=64: one-wave groups for k_fri / k_vanish_final on the side stream
-                                    // (measured 1.119-1.121 M against 1.128-1.130 M, profiles/r03l_side_wg.txt)
-  int split_phase1 = 0;             // env P2V_PHASE1=split (1): k_transcript (side stream) + k_leaf instead of k_phase1.
-                                    // Measured (profiles/r02_phase1_split.txt): serial 0.94x, pipelined 1.00x; the
-                                    // transcript waves, latency-bound, stretch to 2.9 ms beside k_leaf.
-                                    // P2V_PHASE1=excl (2): k_transcript_x (main stream, a SIMD per wave) + k_leaf (side)
   bool debug_sync = false;          // env P2V_DEBUG_SYNC=1: name each launch on stderr and synchronise after it (fault isolation)
   // JSON ingest on the device (p2v_verifier_run_json): the current template and its device
   // form, and buffers grown on demand
@@ -442,7 +433,6 @@ void p2v_verifier_free(p2v_verifier* v) {
   if (v->timed) for (auto& e : v->ev) (void)hipEventDestroy(e);
   if (v->dep_p1) (void)hipEventDestroy(v->dep_p1);
   if (v->dep_side) (void)hipEventDestroy(v->dep_side);
-  if (v->dep_tr) (void)hipEventDestroy(v->dep_tr);
   if (v->p1_done) (void)hipEventDestroy(v->p1_done);
   if (v->side) (void)hipStreamDestroy(v->side);
   if (v->side2) (void)hipStreamDestroy(v->side2);
@@ -482,11 +472,7 @@ int p2v_verifier_create(const p2v_circuit* pc, int device, size_t max_batch, p2v
   v->circ = pc; v->device = device; v->max_batch = max_batch;
   v->Bmax = (max_batch + 63) / 64 * 64;
   if (const char* ss = getenv("P2V_SINGLE_STREAM")) v->single_stream = ss[0] == '1';
-  if (const char* sp = getenv("P2V_SIDE_PRIO")) v->side_prio = sp[0] == '1';
   if (const char* ds = getenv("P2V_DEBUG_SYNC")) v->debug_sync = ds[0] == '1';
-  if (const char* f1 = getenv("P2V_PHASE1")) v->split_phase1 = !strcmp(f1, "split") ? 1 : !strcmp(f1, "excl") ? 2 : 0;
-  if (const char* ff = getenv("P2V_FRI_FIRST")) v->fri_first = ff[0] == '1';
-  if (const char* sw = getenv("P2V_SIDE_WG")) v->side_wg = atoi(sw) == 64 ? 64 : 256;
   if (const char* lm = getenv("P2V_LANE_MIN")) v->lane_min_batch = atoi(lm) > 0 ? atoi(lm) : v->lane_min_batch;
   if (const char* qm = getenv("P2V_QUAD_MIN")) v->quad_min_batch = atoi(qm) > 0 ? atoi(qm) : v->quad_min_batch;
   if (const char* mc = getenv("P2V_MERKLE_CSE")) v->merkle_cse = mc[0] != '0';
@@ -663,17 +649,10 @@ int p2v_verifier_create(const p2v_circuit* pc, int device, size_t max_batch, p2v
   if (e == hipSuccess) { for (auto& x : v->ev) { e = hipEventCreate(&x); if (e != hipSuccess) break; } v->timed = e == hipSuccess; }
   if (e == hipSuccess) e = hipEventCreateWithFlags(&v->dep_p1, hipEventDisableTiming);
   if (e == hipSuccess) e = hipEventCreateWithFlags(&v->dep_side, hipEventDisableTiming);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&v->dep_tr, hipEventDisableTiming);
   if (e == hipSuccess) e = hipEventCreateWithFlags(&v->p1_done, hipEventDisableTiming);
-  // the side stream carries few, long-latency waves (vanishing items, FRI queries); a
-  // high-priority queue for it was measured (P2V_SIDE_PRIO=1) and changed nothing
-  if (e == hipSuccess) {
-    int least = 0, greatest = 0;
-    if (v->side_prio && hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess)
-      e = hipStreamCreateWithPriority(&v->side, hipStreamNonBlocking, greatest);
-    else
-      e = hipStreamCreateWithFlags(&v->side, hipStreamNonBlocking);
-  }
+  // the side stream carries few, long-latency waves (vanishing items, FRI queries), at the default
+  // priority (a high-priority queue changed nothing: DESIGN.md "Retired run-time switches")
+  if (e == hipSuccess) e = hipStreamCreateWithFlags(&v->side, hipStreamNonBlocking);
   // (the latency-mode and lookahead streams are created on first use: every stream a process
   // creates may take one of its few hardware queues, GPU_MAX_HW_QUEUES = 4, and two workspaces'
   // main and side streams must not share one)
@@ -710,6 +689,17 @@ void p2v_tile_proofs(const uint64_t* pm, size_t n, size_t W, uint64_t* tiled) {
         dst[w * 64 + l] = i < n ? pm[i * W + w] : 0;
       }
   }
+}
+
+// the transcript form's kernel (tl lanes per proof; 1: lane, 2: pair, else row / quad): with the
+// leaf hashing in its launch, and on its own (the lookahead path)
+static void launch_phase1(const DevCircuit& d, int tl, int nt_blocks, int leaf_blocks, hipStream_t s) {
+  auto* k = tl == 1 ? k_phase1_lane : tl == 2 ? k_phase1_pair : k_phase1;
+  k<<<nt_blocks + leaf_blocks, 256, 0, s>>>(d, nt_blocks, tl);
+}
+static void launch_transcript(const DevCircuit& d, int tl, int nt_blocks, hipStream_t s) {
+  auto* k = tl == 1 ? k_transcript_lane : tl == 2 ? k_transcript_pair : k_transcript;
+  k<<<nt_blocks, 256, 0, s>>>(d, tl);
 }
 
 int p2v_verifier_run(p2v_verifier* v, const uint64_t* proofs, size_t n, int8_t* results, uint64_t* trace, void* stream_, uint32_t flags) {
@@ -760,9 +750,6 @@ int p2v_verifier_run(p2v_verifier* v, const uint64_t* proofs, size_t n, int8_t* 
   else if (v->transcript_mode == 2) tl = 4;
   else if (v->transcript_mode == 3) tl = 1;
   else if (v->transcript_mode == 4) tl = 2;
-  // P2V_PHASE1=excl (measurement) takes the row or quad transcript only: the lane / pair forms
-  // fall back to the quad form here, before anything is enqueued
-  if (v->split_phase1 == 2 && tl <= 2) tl = 4;
   const int nt_blocks = (tl * d.B + 255) / 256;
   const int leaf_units = d.Q * d.T * NPB;
   // staggered workspaces (p2v_verifier_chain): phase 1 after the linked workspace's latest one
@@ -783,9 +770,7 @@ int p2v_verifier_run(p2v_verifier* v, const uint64_t* proofs, size_t n, int8_t* 
     d.chal = (uint64_t*)(la_slot ? v->chal2.p : v->chal.p);
     HCK(hipStreamWaitEvent(v->ts, v->chal_free[la_slot], 0));
     T0(9, v->ts);
-    if (tl == 1) k_transcript_lane<<<nt_blocks, 256, 0, v->ts>>>(d, tl);
-    else if (tl == 2) k_transcript_pair<<<nt_blocks, 256, 0, v->ts>>>(d, tl);
-    else k_transcript<<<nt_blocks, 256, 0, v->ts>>>(d, tl);
+    launch_transcript(d, tl, nt_blocks, v->ts);
     DBG("k_transcript", v->ts);
     T1(9, v->ts);
     HCK(hipEventRecord(v->tr_done[la_slot], v->ts));
@@ -796,48 +781,15 @@ int p2v_verifier_run(p2v_verifier* v, const uint64_t* proofs, size_t n, int8_t* 
     HCK(hipStreamWaitEvent(st, v->tr_done[la_slot], 0));   // k_merkle reads the query indices
     HCK(hipEventRecord(v->dep_p1, st));                     // the side kernels read the challenges
     HCK(hipStreamWaitEvent(sd, v->dep_p1, 0));
-  } else if (!v->split_phase1 || sd == st) {
+  } else {
     T0(1, st);
-    if (tl == 1) k_phase1_lane<<<nt_blocks + (leaf_units + 3) / 4, 256, 0, st>>>(d, nt_blocks, tl);
-    else if (tl == 2) k_phase1_pair<<<nt_blocks + (leaf_units + 3) / 4, 256, 0, st>>>(d, nt_blocks, tl);
-    else k_phase1<<<nt_blocks + (leaf_units + 3) / 4, 256, 0, st>>>(d, nt_blocks, tl);
+    launch_phase1(d, tl, nt_blocks, (leaf_units + 3) / 4, st);
     DBG("k_phase1", st);
     T1(1, st);
     if (sd != st) {
       HCK(hipEventRecord(v->dep_p1, st));
       HCK(hipStreamWaitEvent(sd, v->dep_p1, 0));
     }
-  } else if (v->split_phase1 == 2) {
-    // the transcripts first, on st, so their waves claim empty SIMDs before the leaf waves land
-    HCK(hipEventRecord(v->dep_p1, st));   // the batch is ready on st
-    T0(9, st);
-    k_transcript_x<<<nt_blocks, 256, 0, st>>>(d, tl);
-    DBG("k_transcript_x", st);
-    T1(9, st);
-    HCK(hipStreamWaitEvent(sd, v->dep_p1, 0));
-    T0(8, sd);
-    k_leaf<<<(leaf_units + 3) / 4, 256, 0, sd>>>(d);
-    DBG("k_leaf", sd);
-    T1(8, sd);
-    HCK(hipEventRecord(v->dep_tr, sd));
-    HCK(hipStreamWaitEvent(st, v->dep_tr, 0));   // k_merkle reads the leaf digests
-    HCK(hipEventRecord(v->dep_p1, st));          // k_fri / the vanishing kernels read the challenges
-    HCK(hipStreamWaitEvent(sd, v->dep_p1, 0));
-  } else {
-    HCK(hipEventRecord(v->dep_p1, st));   // the batch is ready on st (H2D, caller's stream order)
-    HCK(hipStreamWaitEvent(sd, v->dep_p1, 0));
-    T0(9, sd);
-    if (tl == 1) k_transcript_lane<<<nt_blocks, 256, 0, sd>>>(d, tl);
-    else if (tl == 2) k_transcript_pair<<<nt_blocks, 256, 0, sd>>>(d, tl);
-    else k_transcript<<<nt_blocks, 256, 0, sd>>>(d, tl);
-    DBG("k_transcript", sd);
-    T1(9, sd);
-    HCK(hipEventRecord(v->dep_tr, sd));
-    T0(8, st);
-    k_leaf<<<(leaf_units + 3) / 4, 256, 0, st>>>(d);
-    DBG("k_leaf", st);
-    T1(8, st);
-    HCK(hipStreamWaitEvent(st, v->dep_tr, 0));   // k_merkle reads the query indices
   }
   HCK(hipEventRecord(v->p1_done, st));   // k_merkle's inputs are complete on st here in both forms
   v->p1_recorded.store(true, std::memory_order_release);
@@ -849,8 +801,6 @@ int p2v_verifier_run(p2v_verifier* v, const uint64_t* proofs, size_t n, int8_t* 
   const int mk_wg = lat ? 64 : 256;
   const bool fri2 = lat && sd != st;
   if (fri2 && !v->side2) HCK(hipStreamCreateWithFlags(&v->side2, hipStreamNonBlocking));
-  // side-stream work-groups of k_fri / k_vanish_final (P2V_SIDE_WG, measurement)
-  const int side_wg = v->side_wg;
   if (fri2) {
     HCK(hipStreamWaitEvent(v->side2, v->p1_done, 0));
     T0(3, v->side2);
@@ -861,14 +811,6 @@ int p2v_verifier_run(p2v_verifier* v, const uint64_t* proofs, size_t n, int8_t* 
   }
   // phase 2: Merkle paths on the main stream; FRI queries and the vanishing kernel (few,
   // long-latency waves) on the side stream, concurrently
-  // k_fri first: it needs only phase 1 and is the shorter chain, so the vanishing kernels
-  // (longest waves, most registers) are what remains when k_merkle's waves retire
-  if (v->fri_first && !fri2) {
-    T0(3, sd);
-    k_fri<<<(d.Q * NPB * 64 + side_wg - 1) / side_wg, side_wg, 0, sd>>>(d);
-    DBG("k_fri", sd);
-    T1(3, sd);
-  }
   T0(7, sd);
   if (d.n_lut_pieces > 0) k_lut<<<(d.r * d.n_lut_pieces * NPB + 3) / 4, 256, 0, sd>>>(d);
   DBG("k_lut", sd);
@@ -909,12 +851,12 @@ int p2v_verifier_run(p2v_verifier* v, const uint64_t* proofs, size_t n, int8_t* 
   DBG("k_vanish_lookup", sd);
   T1(4, sd);
   T0(6, sd);
-  k_vanish_final<<<(d.B + side_wg - 1) / side_wg, side_wg, 0, sd>>>(d);
+  k_vanish_final<<<(d.B + 255) / 256, 256, 0, sd>>>(d);
   DBG("k_vanish_final", sd);
   T1(6, sd);
-  if (!v->fri_first && !fri2) {
+  if (!fri2) {   // after the vanishing kernels (before them: pipelined -1.5 %, DESIGN.md "Retired run-time switches")
     T0(3, sd);
-    k_fri<<<(d.Q * NPB * 64 + side_wg - 1) / side_wg, side_wg, 0, sd>>>(d);
+    k_fri<<<(d.Q * NPB * 64 + 255) / 256, 256, 0, sd>>>(d);
     DBG("k_fri", sd);
     T1(3, sd);
   }

@@ -67,11 +67,12 @@ __device__ __forceinline__ void leaf_hash_unit(const DevCircuit& c, int unit, in
 
 // The transcript (Challenge/Verifier.hs:58-103, Challenge/FRI.hs:65-104) is a fixed
 // sequence of absorbs and squeezes for a given circuit; the host compiles it into an op
-// program and this loop interprets it with ONE permutation call site.  Each proof's duplex
-// state is spread over a 16-lane row (rposeidon.h): the ~115 permutations form a strictly
-// serial chain, so per-permutation latency, not throughput, is what counts.  Lane L owns
-// state word L, so an absorbed chunk is one load per lane, issued before the pending
-// permutation so that its latency hides behind it.
+// program and one interpreter (transcript() below) runs it for each of the four lane layouts
+// of a proof's duplex state (the forms below).  The ~115 permutations form a strictly serial
+// chain, so per-permutation latency, not throughput, is what counts until the batch's leaf
+// hashing outlasts the chain.
+//
+// the row form's fold of the reduced openings: DPP row rotations (rposeidon.h)
 template <int D>
 __device__ __forceinline__ uint64_t row_up(uint64_t v, bool plus) {   // value of lane L + D (mod 16)
   const uint32_t lo = (uint32_t)v, hi = (uint32_t)(v >> 32);
@@ -104,26 +105,136 @@ __device__ __forceinline__ E horner_strided(const DevCircuit& c, int64_t off, in
   return h;
 }
 
-// the row form's permutation: lposeidon.h (round 5: LDS exchange, merged partial blocks; 8.1-8.6 us
-// per dependent permutation, profiles/r05e_lrow_chain.txt; round 6: chain rows on the idle lanes,
-// 6.6-6.8 us, profiles/r06p_row_par.txt; the DPP form it replaced: DESIGN.md "Retired build
-// options").  R: the row's DPP direction for the reduced openings' fold below (rposeidon.h)
-__device__ __forceinline__ void transcript_row(const DevCircuit& c, int p, const rp::Row& R, const lp::Row& LR, const lp::TLdsL& TL) {
-  const int L = R.L;
-  // public inputs hash, Hash/Sponge.hs:26-31 (sponge [] = zero digest)
-  uint64_t x = 0;
-  for (int i = 0; i < c.num_pis; i += 8) {
-    const int k = c.num_pis - i;
-    if (L < 8 && L < k) x = ld(c, c.pis + i + L, p);
-    x = lp::permute(x, LR, TL);
+// The four lane layouts of a proof's duplex state.  A form says how many lanes share a proof
+// (2^LOG; lane t of them owns the W state words W t .. W t + W - 1, so t == 0 holds word 0 and
+// writes the challenges), how the state is permuted, how a word (wave-uniform position) reaches
+// every lane, and how the lanes' partial sums of the reduced openings fold into lane 0.  The flags
+// keep each form's load shapes, which is what keeps k_phase1 at 128 VGPRs without scratch:
+//   LOAD_FIRST  an absorbed chunk's loads are issued before the pending permutation, so their
+//               latency hides under it (else after it: no registers held across it)
+//   CLAMP       a lane loads from a clamped address and selects (else loads only what it owns)
+//   SUMS_FIRST  both reduced-opening sums are formed before either is folded
+
+// Row form: lposeidon.h (LDS exchange, merged partial blocks, chain rows on the idle lanes: 6.6-6.8
+// us per dependent permutation, profiles/r06p_row_par.txt); lanes 12..15 own no word.  The ~115
+// permutations form a strictly serial chain, so this form has the lowest latency.
+struct RowForm {
+  static constexpr int W = 1, LOG = 4;
+  static constexpr bool LOAD_FIRST = true, CLAMP = false, SUMS_FIRST = false;
+  const lp::Row& LR;
+  const lp::TLdsL& TL;
+  const int t;
+  const bool plus;   // the row rotation's direction, for the fold (rposeidon.h)
+  __device__ __forceinline__ RowForm(const lp::Row& lr, const lp::TLdsL& tl) : LR(lr), TL(tl), t(lr.L), plus(rp::ror_plus(lr.L)) {}
+  __device__ __forceinline__ void permute(uint64_t (&x)[1]) const { x[0] = lp::permute(x[0], LR, TL); }
+  __device__ __forceinline__ uint64_t get_word(const uint64_t (&x)[1], int pos) const { return rp::get_word(x[0], pos); }
+  // a block of public inputs (k left, from proof word a) into the rate positions
+  __device__ __forceinline__ void load_pis(const DevCircuit& c, int p, int64_t a, int k, uint64_t (&x)[1]) const {
+    if (t < 8 && t < k) x[0] = ld(c, a + t, p);
+  }
+  __device__ __forceinline__ E fold(E h, const E (&ap)[5]) const {   // a 4-level DPP tree: sum_t alpha^t H_t in lane 0
+    h = row_fold<1>(h, ap[0], plus);
+    h = row_fold<2>(h, ap[1], plus);
+    h = row_fold<4>(h, ap[2], plus);
+    return row_fold<8>(h, ap[3], plus);
+  }
+};
+
+// Quad form (qposeidon.h): higher per-permutation latency than the row form but ~2.3x fewer issue
+// slots in total, which is what matters once the batch is large enough that the transcript hides
+// behind the leaf hashing sharing its launch (the host picks the form, see api.cpp).
+struct QuadForm {
+  static constexpr int W = 3, LOG = 2;
+  static constexpr bool LOAD_FIRST = true, CLAMP = true, SUMS_FIRST = true;
+  const int t;
+  const qp::TLds& T;
+  __device__ __forceinline__ void permute(uint64_t (&x)[3]) const { qp::permute(x, t, T); }
+  __device__ __forceinline__ uint64_t get_word(const uint64_t (&x)[3], int pos) const { return qp::get_word(x, pos); }
+  __device__ __forceinline__ void load_pis(const DevCircuit& c, int p, int64_t a, int k, uint64_t (&x)[3]) const {
+    for (int j = 0; j < 8 && j < k; j++) qp::set_word(x, t, j, ld(c, a + j, p));
+  }
+  __device__ __forceinline__ E fold(E h, const E (&ap)[3]) const {
+    const E alpha = ap[0];
+    E h1{qp::bcast64(h.a, 1), qp::bcast64(h.b, 1)};
+    E h2{qp::bcast64(h.a, 2), qp::bcast64(h.b, 2)};
+    E h3{qp::bcast64(h.a, 3), qp::bcast64(h.b, 3)};
+    E h0{qp::bcast64(h.a, 0), qp::bcast64(h.b, 0)};
+    return gl::eadd(h0, gl::emul(alpha, gl::eadd(h1, gl::emul(alpha, gl::eadd(h2, gl::emul(alpha, h3))))));
+  }
+};
+
+// Pair form (pposeidon.h; lane 1 owns rate positions 6, 7): about half of the quad's instructions
+// per proof at a shorter chain than the lane form's (P2V_TRANSCRIPT=pair)
+struct PairForm {
+  static constexpr int W = 6, LOG = 1;
+  static constexpr bool LOAD_FIRST = true, CLAMP = true, SUMS_FIRST = false;
+  const int t;
+  const pp::TLdsP& T;
+  __device__ __forceinline__ void permute(uint64_t (&x)[6]) const { pp::permute(x, t, T); }
+  __device__ __forceinline__ uint64_t get_word(const uint64_t (&x)[6], int pos) const { return pp::get_word(x, pos); }
+  __device__ __forceinline__ void load_pis(const DevCircuit& c, int p, int64_t a, int k, uint64_t (&x)[6]) const {
+#pragma unroll
+    for (int j = 0; j < 6; j++) {   // selects, not divergent stores: x stays in registers
+      const int pos = 6 * t + j;
+      const bool mine = pos < 8 && pos < k;
+      const uint64_t v = ld(c, a + (mine ? pos : 0), p);
+      x[j] = mine ? v : x[j];
+    }
+  }
+  __device__ __forceinline__ E fold(E h, const E (&ap)[2]) const {
+    const E h0{pp::bcast64(h.a, 0), pp::bcast64(h.b, 0)}, h1{pp::bcast64(h.a, 1), pp::bcast64(h.b, 1)};
+    return gl::eadd(h0, gl::emul(ap[0], h1));
+  }
+};
+
+// Lane form: the whole state in one lane's registers, the throughput permutation.  About half of
+// the quad form's VALU instructions per proof (85.9 M against 169.4 M per 4096 proofs, DESIGN.md
+// §7.0), but a chain ~3.5x longer (a lone wave issues its dependent permutation at its own
+// latency): for launches whose leaf hashing outlasts it (api.cpp, P2V_TRANSCRIPT=lane).
+struct LaneForm {
+  static constexpr int W = 12, LOG = 0;
+  static constexpr bool LOAD_FIRST = false, CLAMP = false, SUMS_FIRST = false;
+  static constexpr int t = 0;
+  __device__ __forceinline__ void permute(uint64_t (&x)[12]) const { p2::permute_dev<false>(x); }
+  __device__ __forceinline__ void load_pis(const DevCircuit& c, int p, int64_t a, int k, uint64_t (&x)[12]) const {
+#pragma unroll
+    for (int j = 0; j < 8; j++) if (j < k) x[j] = ld(c, a + j, p);
+  }
+  __device__ __forceinline__ uint64_t get_word(const uint64_t (&x)[12], int pos) const {
+    switch (pos) {   // uniform: a switch, not a dynamically indexed (scratch) array
+      case 0: return x[0];
+      case 1: return x[1];
+      case 2: return x[2];
+      case 3: return x[3];
+      case 4: return x[4];
+      case 5: return x[5];
+      case 6: return x[6];
+      default: return x[7];
+    }
+  }
+  __device__ __forceinline__ E fold(E h, const E (&)[1]) const { return h; }
+};
+
+// The interpreter, written once for the four forms: ONE permutation call site per duplex rule
+template <class F>
+__device__ __forceinline__ void transcript(const DevCircuit& c, int p, const F& f) {
+  const bool leader = f.t == 0;
+  constexpr int RW = F::W < 8 ? F::W : 8;   // a lane's words that can be rate positions
+  uint64_t x[F::W];
+#pragma unroll
+  for (int i = 0; i < F::W; i++) x[i] = 0;
+  for (int i = 0; i < c.num_pis; i += 8) {   // public inputs hash, Hash/Sponge.hs:26-31 (sponge [] = zero digest)
+    f.load_pis(c, p, c.pis + i, c.num_pis - i, x);
+    f.permute(x);
   }
   uint64_t pih[4];
 #pragma unroll
   for (int w = 0; w < 4; w++) {
-    pih[w] = rp::get_word(x, w);
-    if (L == 0) chal(c, CH_PI(c) + w, p) = pih[w];
+    pih[w] = f.get_word(x, w);
+    if (leader) chal(c, CH_PI(c) + w, p) = pih[w];
   }
-  x = 0;
+#pragma unroll
+  for (int i = 0; i < F::W; i++) x[i] = 0;
   int nbuf = 0, outpos = -1;
   bool absorbing = true;
   const uint64_t qmask = (1ULL << c.lde_bits) - 1;
@@ -131,11 +242,11 @@ __device__ __forceinline__ void transcript_row(const DevCircuit& c, int p, const
   for (int o = 0; o < c.ntops; o++) {
     const int type = c.tops[3 * o], a = c.tops[3 * o + 1], n = c.tops[3 * o + 2];
     if (type == TOP_COPY) {   // mkLookupDeltaList (betas ++ gammas ++ ...), Challenge/Verifier.hs:36-40,82-86
-      if (L == 0) for (int k = 0; k < n; k++) chal(c, a + k, p) = chal(c, a - 3 * c.r + k, p);
+      if (leader) for (int k = 0; k < n; k++) chal(c, a + k, p) = chal(c, a - 3 * c.r + k, p);
       continue;
     }
     if (type == TOP_ZERO) {
-      if (L == 0) for (int k = 0; k < n; k++) chal(c, a + k, p) = 0;
+      if (leader) for (int k = 0; k < n; k++) chal(c, a + k, p) = 0;
       continue;
     }
     if (type <= TOP_ABSORB_DIGEST) {   // absorb n words, chunk by chunk (lazy duplex, Challenge/Pure.hs:38-69)
@@ -143,292 +254,55 @@ __device__ __forceinline__ void transcript_row(const DevCircuit& c, int p, const
       for (int k = 0; k < n;) {
         const int start = nbuf == 8 ? 0 : nbuf;
         const int take = (8 - start) < (n - k) ? (8 - start) : (n - k);
-        const int j = k + L - start;   // this lane's word of the chunk
-        const bool mine = L >= start && L < start + take;
-        uint64_t v = 0;
-        if (type == TOP_ABSORB_SOA) { if (mine) v = ld(c, (int64_t)a + j, p); }
-        else if (type == TOP_ABSORB_PIH) { const int w = j & 3; v = w == 0 ? pih[0] : w == 1 ? pih[1] : w == 2 ? pih[2] : pih[3]; }
-        else v = c.digest[j & 3];
-        if (nbuf == 8) { x = lp::permute(x, LR, TL); nbuf = 0; }   // overwrite mode: the rate part is replaced
-        if (mine) x = v;
-        nbuf += take;
+        // word k + pos - start of the source replaces rate position pos, start <= pos < start + take;
+        // before that the pending permutation of a full block (overwrite mode: the rate part is replaced)
+        const bool full = nbuf == 8;
+        if (full && !F::LOAD_FIRST) f.permute(x);
+        uint64_t v[RW];
+        bool mine[RW];
+#pragma unroll
+        for (int j = 0; j < RW; j++) {
+          const int pos = F::W * f.t + j, w = k + pos - start;
+          mine[j] = pos >= start && pos < start + take;
+          v[j] = 0;
+          if (type == TOP_ABSORB_SOA) {
+            if constexpr (F::CLAMP) { const uint64_t u = ld(c, (int64_t)a + (mine[j] ? w : 0), p); v[j] = mine[j] ? u : 0; }
+            else { if (mine[j]) v[j] = ld(c, (int64_t)a + w, p); }
+          } else if (type == TOP_ABSORB_PIH) { const int q = w & 3; v[j] = q == 0 ? pih[0] : q == 1 ? pih[1] : q == 2 ? pih[2] : pih[3]; }
+          else v[j] = c.digest[w & 3];
+        }
+        if (full && F::LOAD_FIRST) f.permute(x);
+#pragma unroll
+        for (int j = 0; j < RW; j++) x[j] = mine[j] ? v[j] : x[j];   // selects, not divergent stores: x stays in registers
+        nbuf = start + take;
         k += take;
       }
       continue;
     }
     for (int k = 0; k < n; k++) {   // squeeze: output order state[7], state[6], ... (reverse of take 8)
-      if (absorbing || outpos < 0) { x = lp::permute(x, LR, TL); absorbing = false; outpos = 7; }
-      uint64_t w = rp::get_word(x, outpos);
+      if (absorbing || outpos < 0) { f.permute(x); absorbing = false; outpos = 7; }   // duplex / re-permute
+      uint64_t w = f.get_word(x, outpos);
       outpos--;
       if (type == TOP_SQUEEZE_IDX) w &= qmask;
       if (a + k == CH_FRI_ALPHA(c)) fa0 = w;
       if (a + k == CH_FRI_ALPHA(c) + 1) fa1 = w;
-      if (L == 0) chal(c, a + k, p) = w;
+      if (leader) chal(c, a + k, p) = w;
     }
   }
-  // precomputeReducedOpenings, Plonk/FRI.hs:128-134: Y = sum alpha^i y_i.  Split over the
-  // row: lane L sums the terms i = L (mod 16) in powers of alpha^16, then a 4-level DPP tree
-  // forms sum_L alpha^L H_L in lane 0.
-  const E alpha{fa0, fa1};
-  const E a2 = gl::emul(alpha, alpha), a4 = gl::emul(a2, a2), a8 = gl::emul(a4, a4), a16 = gl::emul(a8, a8);
+  // precomputeReducedOpenings, Plonk/FRI.hs:128-134: Y = sum alpha^i y_i.  Lane t of the S = 2^LOG
+  // lanes sums the terms i = t (mod S) in powers of alpha^S (Horner from the top), then the form
+  // folds Y = sum_t alpha^t H_t into lane 0.  ap[s] = alpha^(2^s)
+  E ap[F::LOG + 1] = {E{fa0, fa1}};
 #pragma unroll
-  for (int b = 0; b < 2; b++) {
-    const int64_t n = b == 0 ? c.n_this : c.n_next, off = b == 0 ? c.o_const : c.o_zs_next;
-    E h = horner_strided<16>(c, off, n, L, p, a16);
-    h = row_fold<1>(h, alpha, R.plus);
-    h = row_fold<2>(h, a2, R.plus);
-    h = row_fold<4>(h, a4, R.plus);
-    h = row_fold<8>(h, a8, R.plus);
-    if (L == 0) { chal(c, (b == 0 ? CH_Y0(c) : CH_Y1(c)), p) = h.a; chal(c, (b == 0 ? CH_Y0(c) : CH_Y1(c)) + 1, p) = h.b; }
-  }
-}
-
-// Quad form of the same transcript (qposeidon.h: 4 lanes per proof, 3 state words per
-// lane).  Higher per-permutation latency than the row form but ~2.3x fewer issue slots in
-// total, which is what matters once the batch is large enough that the transcript hides
-// behind the leaf hashing sharing its launch (the host picks the form, see api.cpp).
-__device__ __forceinline__ void transcript_quad(const DevCircuit& c, int p, int t, const qp::TLds& T) {
-  // public inputs hash, Hash/Sponge.hs:26-31 (sponge [] = zero digest)
-  uint64_t x[3] = {0, 0, 0};
-  for (int i = 0; i < c.num_pis; i += 8) {
-    const int k = c.num_pis - i;
-    for (int j = 0; j < 8 && j < k; j++) qp::set_word(x, t, j, ld(c, c.pis + i + j, p));
-    qp::permute(x, t, T);
-  }
-  uint64_t pih[4];
-#pragma unroll
-  for (int w = 0; w < 4; w++) {
-    pih[w] = qp::get_word(x, w);
-    if (t == 0) chal(c, CH_PI(c) + w, p) = pih[w];
-  }
-  x[0] = x[1] = x[2] = 0;
-  int nbuf = 0, outpos = -1;
-  bool absorbing = true;
-  const uint64_t qmask = (1ULL << c.lde_bits) - 1;
-  uint64_t fa0 = 0, fa1 = 0;   // FRI alpha, kept in registers for the reduced openings below
-  for (int o = 0; o < c.ntops; o++) {
-    const int type = c.tops[3 * o], a = c.tops[3 * o + 1], n = c.tops[3 * o + 2];
-    if (type == TOP_COPY) {   // mkLookupDeltaList (betas ++ gammas ++ ...), Challenge/Verifier.hs:36-40,82-86
-      if (t == 0) for (int k = 0; k < n; k++) chal(c, a + k, p) = chal(c, a - 3 * c.r + k, p);
-      continue;
-    }
-    if (type == TOP_ZERO) {
-      if (t == 0) for (int k = 0; k < n; k++) chal(c, a + k, p) = 0;
-      continue;
-    }
-    if (type <= TOP_ABSORB_DIGEST) {   // absorb n words, chunk by chunk (lazy duplex, Challenge/Pure.hs:38-69)
-      if (!absorbing) { absorbing = true; nbuf = 0; }
-      for (int k = 0; k < n;) {
-        const int start = nbuf == 8 ? 0 : nbuf;
-        const int take = (8 - start) < (n - k) ? (8 - start) : (n - k);
-        // lane t owns rate positions 3t..3t+2 (qposeidon.h); the chunk's loads are issued
-        // before the permutation so their HBM latency hides under it
-        uint64_t v[3];
-        bool mine[3];
-#pragma unroll
-        for (int j = 0; j < 3; j++) {
-          const int pos = 3 * t + j, w = k + pos - start;
-          mine[j] = pos >= start && pos < start + take;
-          v[j] = 0;
-          if (type == TOP_ABSORB_SOA) { const uint64_t u = ld(c, (int64_t)a + (mine[j] ? w : 0), p); v[j] = mine[j] ? u : 0; }
-          else if (type == TOP_ABSORB_PIH) { const int q = w & 3; v[j] = q == 0 ? pih[0] : q == 1 ? pih[1] : q == 2 ? pih[2] : pih[3]; }
-          else v[j] = c.digest[w & 3];
-        }
-        if (nbuf == 8) { qp::permute(x, t, T); nbuf = 0; }   // overwrite mode: the rate part is replaced
-#pragma unroll
-        for (int j = 0; j < 3; j++) x[j] = mine[j] ? v[j] : x[j];
-        nbuf += take;
-        k += take;
-      }
-      continue;
-    }
-    for (int k = 0; k < n; k++) {   // squeeze
-      const bool need = absorbing || outpos < 0;
-      if (need) { qp::permute(x, t, T); absorbing = false; outpos = 7; }   // duplex / re-permute, Challenge/Pure.hs:38-69
-      uint64_t w = qp::get_word(x, outpos);   // output order state[7], state[6], ... (reverse of take 8)
-      outpos--;
-      if (type == TOP_SQUEEZE_IDX) w &= qmask;
-      if (a + k == CH_FRI_ALPHA(c)) fa0 = w;
-      if (a + k == CH_FRI_ALPHA(c) + 1) fa1 = w;
-      if (t == 0) chal(c, a + k, p) = w;
-    }
-  }
-  // precomputeReducedOpenings, Plonk/FRI.hs:128-134: Y = sum alpha^i y_i.  Split over the
-  // quad: lane t sums the terms i = t (mod 4) in powers of alpha^4, then Y = sum_t alpha^t H_t.
-  const E alpha{fa0, fa1};
-  const E al2 = gl::emul(alpha, alpha), al4 = gl::emul(al2, al2);
+  for (int s = 1; s <= F::LOG; s++) ap[s] = gl::emul(ap[s - 1], ap[s - 1]);
   E H[2];
 #pragma unroll
-  for (int b = 0; b < 2; b++) {
-    const int64_t n = b == 0 ? c.n_this : c.n_next, off = b == 0 ? c.o_const : c.o_zs_next;
-    H[b] = horner_strided<4>(c, off, n, t, p, al4);
-  }
+  for (int b = 0; b < 2 * F::SUMS_FIRST; b++) H[b] = horner_strided<1 << F::LOG>(c, b == 0 ? c.o_const : c.o_zs_next, b == 0 ? c.n_this : c.n_next, f.t, p, ap[F::LOG]);
 #pragma unroll
   for (int b = 0; b < 2; b++) {
-    E h1{qp::bcast64(H[b].a, 1), qp::bcast64(H[b].b, 1)};
-    E h2{qp::bcast64(H[b].a, 2), qp::bcast64(H[b].b, 2)};
-    E h3{qp::bcast64(H[b].a, 3), qp::bcast64(H[b].b, 3)};
-    E h0{qp::bcast64(H[b].a, 0), qp::bcast64(H[b].b, 0)};
-    const E y = gl::eadd(h0, gl::emul(alpha, gl::eadd(h1, gl::emul(alpha, gl::eadd(h2, gl::emul(alpha, h3))))));
-    if (t == 0) { chal(c, (b == 0 ? CH_Y0(c) : CH_Y1(c)), p) = y.a; chal(c, (b == 0 ? CH_Y0(c) : CH_Y1(c)) + 1, p) = y.b; }
-  }
-}
-
-// Lane form of the same transcript: one lane per proof, the whole state in its registers, the
-// throughput permutation (p2::permute_dev).  About half of the quad form's VALU instructions per
-// proof (85.9 M against 169.4 M per 4096 proofs), but a chain ~3.5x longer (a lone wave issues its dependent permutation at its own
-// latency): for pipelines with enough batches in flight to hide it (round 4, P2V_TRANSCRIPT=lane).
-__device__ __forceinline__ void transcript_lane(const DevCircuit& c, int p) {
-  uint64_t x[12];
-#pragma unroll
-  for (int i = 0; i < 12; i++) x[i] = 0;
-  for (int i = 0; i < c.num_pis; i += 8) {   // public inputs hash, Hash/Sponge.hs:26-31
-    const int k = c.num_pis - i;
-#pragma unroll
-    for (int j = 0; j < 8; j++) if (j < k) x[j] = ld(c, c.pis + i + j, p);
-    p2::permute_dev<false>(x);
-  }
-  uint64_t pih[4];
-#pragma unroll
-  for (int w = 0; w < 4; w++) { pih[w] = x[w]; chal(c, CH_PI(c) + w, p) = pih[w]; }
-#pragma unroll
-  for (int i = 0; i < 12; i++) x[i] = 0;
-  int nbuf = 0, outpos = -1;
-  bool absorbing = true;
-  const uint64_t qmask = (1ULL << c.lde_bits) - 1;
-  uint64_t fa0 = 0, fa1 = 0;
-  for (int o = 0; o < c.ntops; o++) {
-    const int type = c.tops[3 * o], a = c.tops[3 * o + 1], n = c.tops[3 * o + 2];
-    if (type == TOP_COPY) { for (int k = 0; k < n; k++) chal(c, a + k, p) = chal(c, a - 3 * c.r + k, p); continue; }
-    if (type == TOP_ZERO) { for (int k = 0; k < n; k++) chal(c, a + k, p) = 0; continue; }
-    if (type <= TOP_ABSORB_DIGEST) {   // absorb n words, chunk by chunk (lazy duplex, Challenge/Pure.hs:38-69)
-      if (!absorbing) { absorbing = true; nbuf = 0; }
-      for (int k = 0; k < n;) {
-        const int start = nbuf == 8 ? 0 : nbuf;
-        const int take = (8 - start) < (n - k) ? (8 - start) : (n - k);
-        if (nbuf == 8) { p2::permute_dev<false>(x); nbuf = 0; }   // overwrite mode: the rate part is replaced
-#pragma unroll
-        for (int j = 0; j < 8; j++) {   // (loaded after the permutation: no registers held across it)
-          const int w = k + j - start;
-          if (j < start || j >= start + take) continue;
-          if (type == TOP_ABSORB_SOA) x[j] = ld(c, (int64_t)a + w, p);
-          else if (type == TOP_ABSORB_PIH) { const int q = w & 3; x[j] = q == 0 ? pih[0] : q == 1 ? pih[1] : q == 2 ? pih[2] : pih[3]; }
-          else x[j] = c.digest[w & 3];
-        }
-        nbuf += take;
-        k += take;
-      }
-      continue;
-    }
-    for (int k = 0; k < n; k++) {   // squeeze: output order state[7], state[6], ...
-      if (absorbing || outpos < 0) { p2::permute_dev<false>(x); absorbing = false; outpos = 7; }
-      uint64_t w;
-      switch (outpos) {   // uniform: a switch, not a dynamically indexed (scratch) array
-        case 0: w = x[0]; break;
-        case 1: w = x[1]; break;
-        case 2: w = x[2]; break;
-        case 3: w = x[3]; break;
-        case 4: w = x[4]; break;
-        case 5: w = x[5]; break;
-        case 6: w = x[6]; break;
-        default: w = x[7]; break;
-      }
-      outpos--;
-      if (type == TOP_SQUEEZE_IDX) w &= qmask;
-      if (a + k == CH_FRI_ALPHA(c)) fa0 = w;
-      if (a + k == CH_FRI_ALPHA(c) + 1) fa1 = w;
-      chal(c, a + k, p) = w;
-    }
-  }
-  // precomputeReducedOpenings, Plonk/FRI.hs:128-134: Y = sum alpha^i y_i, Horner from the top
-  const E alpha{fa0, fa1};
-#pragma unroll
-  for (int b = 0; b < 2; b++) {
-    const int64_t n = b == 0 ? c.n_this : c.n_next, off = b == 0 ? c.o_const : c.o_zs_next;
-    const E y = horner_strided<1>(c, off, n, 0, p, alpha);
-    chal(c, (b == 0 ? CH_Y0(c) : CH_Y1(c)), p) = y.a;
-    chal(c, (b == 0 ? CH_Y0(c) : CH_Y1(c)) + 1, p) = y.b;
-  }
-}
-
-// Pair form (pposeidon.h: 2 lanes per proof, 6 state words per lane): about half of the quad's
-// instructions per proof at a shorter chain (round 4)
-__device__ __forceinline__ void transcript_pair(const DevCircuit& c, int p, int t, const pp::TLdsP& T) {
-  uint64_t x[6] = {0, 0, 0, 0, 0, 0};
-  for (int i = 0; i < c.num_pis; i += 8) {   // public inputs hash, Hash/Sponge.hs:26-31
-    const int k = c.num_pis - i;
-#pragma unroll
-    for (int j = 0; j < 6; j++) {   // selects, not divergent stores: x stays in registers
-      const int pos = 6 * t + j;
-      const bool mine = pos < 8 && pos < k;
-      const uint64_t v = ld(c, c.pis + i + (mine ? pos : 0), p);
-      x[j] = mine ? v : x[j];
-    }
-    pp::permute(x, t, T);
-  }
-  uint64_t pih[4];
-#pragma unroll
-  for (int w = 0; w < 4; w++) {
-    pih[w] = pp::get_word(x, w);
-    if (t == 0) chal(c, CH_PI(c) + w, p) = pih[w];
-  }
-#pragma unroll
-  for (int j = 0; j < 6; j++) x[j] = 0;
-  int nbuf = 0, outpos = -1;
-  bool absorbing = true;
-  const uint64_t qmask = (1ULL << c.lde_bits) - 1;
-  uint64_t fa0 = 0, fa1 = 0;
-  for (int o = 0; o < c.ntops; o++) {
-    const int type = c.tops[3 * o], a = c.tops[3 * o + 1], n = c.tops[3 * o + 2];
-    if (type == TOP_COPY) { if (t == 0) for (int k = 0; k < n; k++) chal(c, a + k, p) = chal(c, a - 3 * c.r + k, p); continue; }
-    if (type == TOP_ZERO) { if (t == 0) for (int k = 0; k < n; k++) chal(c, a + k, p) = 0; continue; }
-    if (type <= TOP_ABSORB_DIGEST) {   // absorb n words, chunk by chunk (lazy duplex, Challenge/Pure.hs:38-69)
-      if (!absorbing) { absorbing = true; nbuf = 0; }
-      for (int k = 0; k < n;) {
-        const int start = nbuf == 8 ? 0 : nbuf;
-        const int take = (8 - start) < (n - k) ? (8 - start) : (n - k);
-        // lane t owns rate positions 6t .. 6t+5 (lane 1: 6, 7); the chunk's loads before the
-        // permutation so their latency hides under it
-        uint64_t v[6];
-        bool mine[6];
-#pragma unroll
-        for (int j = 0; j < 6; j++) {
-          const int pos = 6 * t + j, w = k + pos - start;
-          mine[j] = pos >= start && pos < start + take;
-          v[j] = 0;
-          if (type == TOP_ABSORB_SOA) { const uint64_t u = ld(c, (int64_t)a + (mine[j] ? w : 0), p); v[j] = mine[j] ? u : 0; }
-          else if (type == TOP_ABSORB_PIH) { const int q = w & 3; v[j] = q == 0 ? pih[0] : q == 1 ? pih[1] : q == 2 ? pih[2] : pih[3]; }
-          else v[j] = c.digest[w & 3];
-        }
-        if (nbuf == 8) { pp::permute(x, t, T); nbuf = 0; }   // overwrite mode: the rate part is replaced
-#pragma unroll
-        for (int j = 0; j < 6; j++) x[j] = mine[j] ? v[j] : x[j];
-        nbuf += take;
-        k += take;
-      }
-      continue;
-    }
-    for (int k = 0; k < n; k++) {   // squeeze: output order state[7], state[6], ...
-      if (absorbing || outpos < 0) { pp::permute(x, t, T); absorbing = false; outpos = 7; }
-      uint64_t w = pp::get_word(x, outpos);
-      outpos--;
-      if (type == TOP_SQUEEZE_IDX) w &= qmask;
-      if (a + k == CH_FRI_ALPHA(c)) fa0 = w;
-      if (a + k == CH_FRI_ALPHA(c) + 1) fa1 = w;
-      if (t == 0) chal(c, a + k, p) = w;
-    }
-  }
-  // precomputeReducedOpenings, Plonk/FRI.hs:128-134: lane t sums the terms i = t (mod 2) in
-  // powers of alpha^2, then Y = H_0 + alpha H_1
-  const E alpha{fa0, fa1};
-  const E al2 = gl::emul(alpha, alpha);
-#pragma unroll
-  for (int b = 0; b < 2; b++) {
-    const int64_t n = b == 0 ? c.n_this : c.n_next, off = b == 0 ? c.o_const : c.o_zs_next;
-    const E h = horner_strided<2>(c, off, n, t, p, al2);
-    const E h0{pp::bcast64(h.a, 0), pp::bcast64(h.b, 0)}, h1{pp::bcast64(h.a, 1), pp::bcast64(h.b, 1)};
-    const E y = gl::eadd(h0, gl::emul(alpha, h1));
-    if (t == 0) { chal(c, (b == 0 ? CH_Y0(c) : CH_Y1(c)), p) = y.a; chal(c, (b == 0 ? CH_Y0(c) : CH_Y1(c)) + 1, p) = y.b; }
+    if constexpr (!F::SUMS_FIRST) H[b] = horner_strided<1 << F::LOG>(c, b == 0 ? c.o_const : c.o_zs_next, b == 0 ? c.n_this : c.n_next, f.t, p, ap[F::LOG]);
+    const E y = f.fold(H[b], ap);
+    if (leader) { chal(c, (b == 0 ? CH_Y0(c) : CH_Y1(c)), p) = y.a; chal(c, (b == 0 ? CH_Y0(c) : CH_Y1(c)) + 1, p) = y.b; }
   }
 }
 
@@ -441,21 +315,16 @@ union TLdsAny { qp::TLds q; pp::TLdsP p; lp::TLdsL l; };
 template <int FORM = 0>
 __device__ __forceinline__ void transcript_block(const DevCircuit& c, int tl, TLdsAny& U) {
   const int g = blockIdx.x * 256 + threadIdx.x;
-  const qp::TLds& T = U.q;
   if constexpr (FORM == 1) {
-    (void)tl; (void)T;
-    if (g < c.B) transcript_lane(c, g);
+    if (g < c.B) transcript(c, g, LaneForm{});
   } else if constexpr (FORM == 2) {
-    (void)tl;
-    if ((g >> 1) < c.B) transcript_pair(c, g >> 1, g & 1, U.p);
+    if ((g >> 1) < c.B) transcript(c, g >> 1, PairForm{g & 1, U.p});
   } else if (tl == 16) {
-    rp::Row R;
-    rp::init(R, threadIdx.x);
     lp::Row LR;
     lp::init(LR, U.l, threadIdx.x);
-    if ((g >> 4) < c.B) transcript_row(c, g >> 4, R, LR, U.l);
+    if ((g >> 4) < c.B) transcript(c, g >> 4, RowForm(LR, U.l));
   } else {
-    if ((g >> 2) < c.B) transcript_quad(c, g >> 2, g & 3, T);
+    if ((g >> 2) < c.B) transcript(c, g >> 2, QuadForm{g & 3, U.q});
   }
 }
 
@@ -496,17 +365,16 @@ extern "C" __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_pe
   phase1_body<2>(c, nt_blocks, tl);
 }
 
-// The same two halves as separate launches (env P2V_PHASE1=split, api.cpp): on their own the leaf
-// waves run at the permutation's 72 VGPRs (7 waves/SIMD) instead of inheriting the transcript's
-// 123 (4 waves/SIMD), the transcript on the side stream beside them.  Measured slower (serial
-// 0.94x): the transcript chains then stretch to the leaf kernel's length; kept for measurement.
+// The same two halves as separate launches, for the transcript lookahead (P2V_FLAG_LOOKAHEAD,
+// api.cpp): the transcript on a stream of its own, one batch ahead of the leaf hashing.  (As the
+// default form of phase 1 they measured slower: DESIGN.md "Retired run-time switches".)
 extern "C" __global__ void __launch_bounds__(256) k_transcript(DevCircuit c, int tl) {
   __builtin_amdgcn_s_setprio(3);
   __shared__ TLdsAny T;
   tlds_fill_form(T, tl);
   transcript_block(c, tl, T);
 }
-// the lane and pair forms on their own (the lookahead / split launches, api.cpp)
+// the lane and pair forms on their own
 extern "C" __global__ void __launch_bounds__(256) k_transcript_lane(DevCircuit c, int tl) {
   __builtin_amdgcn_s_setprio(3);
   __shared__ TLdsAny T;
@@ -517,15 +385,6 @@ extern "C" __global__ void __launch_bounds__(256) k_transcript_pair(DevCircuit c
   __shared__ TLdsAny T;
   pp::tlds_fill(T.p, threadIdx.x, 256);
   transcript_block<2>(c, tl, T);
-}
-// k_transcript with SIMDs of its own: the clobbers below make the kernel allocate the whole
-// register file (256 VGPRs + 256 AGPRs), so each transcript wave is alone on its SIMD and issues
-// at the single-wave latency (lat.hip) instead of sharing issue with co-resident leaf waves.
-extern "C" __global__ void __launch_bounds__(256) k_transcript_x(DevCircuit c, int tl) {
-  asm volatile("" ::: "v255", "a255");
-  __shared__ TLdsAny T;
-  tlds_fill_form(T, tl);
-  transcript_block(c, tl, T);
 }
 extern "C" __global__ void __launch_bounds__(256) k_leaf(DevCircuit c) {
   const int unit = (int)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -875,12 +734,10 @@ extern "C" __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_pe
   if ((int64_t)blockIdx.x * 16 >= nfix) return;   // block-uniform: no entry for this block's rows (honest batches: all)
   tlds_fill_form(T, 16);
   __builtin_amdgcn_s_setprio(3);
-  rp::Row R;   // only R.L is read; dropping the init changes this kernel's register allocation (rposeidon.h)
-  rp::init(R, threadIdx.x);
   lp::Row LR;
   lp::init(LR, T.l, threadIdx.x);
   const lp::TLdsL& TL = T.l;
-  const int L = R.L;
+  const int L = LR.L;
   const int64_t rows = (int64_t)gridDim.x * 16;
   for (int64_t k = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 4; k < nfix; k += rows) {   // row-uniform
     const uint32_t id = c.mfix[k];
