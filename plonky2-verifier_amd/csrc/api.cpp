@@ -7,9 +7,12 @@
 #include <algorithm>
 #include <atomic>
 #include <cstring>
+#include <functional>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <thread>
+#include <utility>
 #include <vector>
 #include "../../include/p2v.h"
 #include "circuit.hpp"
@@ -56,18 +59,64 @@ namespace {
 thread_local std::string g_err;
 int fail(int code, const std::string& msg) { g_err = msg; return code; }
 
+// fn() with the host readers' exceptions as return codes; any other std::exception is `other`
+template <class F>
+int guarded(int other, F fn) {
+  try { fn(); return P2V_OK; }
+  catch (const ShapeError& e) { return fail(P2V_E_SHAPE, e.what()); }
+  catch (const ParseError& e) { return fail(P2V_E_PARSE, e.what()); }
+  catch (const CircuitError& e) { return fail(P2V_E_CIRCUIT, e.what()); }
+  catch (const std::exception& e) { return fail(other, e.what()); }
+}
+
 // per-kernel timing slots; k_fri and k_vanish run on the side stream, concurrently with k_merkle
 // (k_leaf + k_transcript: the two halves of k_phase1 as the lookahead path launches them).
 // Slot 0 is the retired transposing build's; it keeps its name and place (callers index by this
 // list) and is never recorded.
 const char* kKernelNames = "k_transpose,k_phase1,k_merkle,k_fri,k_vanish,k_status,k_vanish_final,k_lut,k_leaf,k_transcript";
-constexpr int kNumKernels = 10;
+enum Slot { SLOT_TRANSPOSE, SLOT_PHASE1, SLOT_MERKLE, SLOT_FRI, SLOT_VANISH, SLOT_STATUS, SLOT_VANISH_FINAL, SLOT_LUT, SLOT_LEAF,
+            SLOT_TRANSCRIPT, kNumKernels };   // the order of kKernelNames
 
-struct DevBuf {
-  void* p = nullptr;
+// Device resources are owned by type: each owner is move-only and releases what it holds in its
+// destructor, on the device that is current then (p2v_verifier_free and pipe_free set it).
+// Device or pinned host memory with its size:
+template <class T, hipError_t (*Alloc)(void**, size_t), hipError_t (*Free)(void*)>
+struct Mem {
+  T* p = nullptr;
   size_t bytes = 0;
-  hipError_t alloc(size_t n) { bytes = n; return hipMalloc(&p, n ? n : 16); }
-  void free_() { if (p) (void)hipFree(p); p = nullptr; }
+  Mem() = default;
+  Mem(Mem&& o) noexcept : p(std::exchange(o.p, nullptr)), bytes(std::exchange(o.bytes, 0)) {}
+  Mem& operator=(Mem&& o) noexcept { std::swap(p, o.p); std::swap(bytes, o.bytes); return *this; }
+  ~Mem() { free_(); }
+  hipError_t alloc(size_t n) {
+    free_();
+    const hipError_t e = Alloc((void**)&p, n ? n : 16);
+    if (e == hipSuccess) bytes = n; else p = nullptr;
+    return e;
+  }
+  hipError_t grow(size_t n) { return n <= bytes ? hipSuccess : alloc(n); }   // never shrinks
+  void free_() { if (p) (void)Free(p); p = nullptr; bytes = 0; }
+};
+hipError_t pinned_alloc(void** p, size_t n) { return hipHostMalloc(p, n); }
+using DevBuf = Mem<void, hipMalloc, hipFree>;
+using PinnedBuf = Mem<int8_t, pinned_alloc, hipHostFree>;
+
+// a stream or an event: empty until created, usable wherever the plain handle is
+template <class H, hipError_t (*Destroy)(H)>
+struct Owned {
+  H h = nullptr;
+  Owned() = default;
+  Owned(Owned&& o) noexcept : h(std::exchange(o.h, nullptr)) {}
+  Owned& operator=(Owned&& o) noexcept { std::swap(h, o.h); return *this; }
+  ~Owned() { if (h) (void)Destroy(h); }
+  operator H() const { return h; }
+};
+struct Stream : Owned<hipStream_t, hipStreamDestroy> {
+  hipError_t create() { return hipStreamCreateWithFlags(&h, hipStreamNonBlocking); }
+};
+struct Event : Owned<hipEvent_t, hipEventDestroy> {
+  hipError_t create() { return hipEventCreateWithFlags(&h, hipEventDisableTiming); }
+  hipError_t create_timed() { return hipEventCreate(&h); }
 };
 }  // namespace
 
@@ -83,10 +132,12 @@ struct p2v_circuit {
 };
 
 namespace {
+// a table on the device, and the DevCircuit field that points to it
 template <class T>
-hipError_t upload(DevBuf& b, const std::vector<T>& h) {
+hipError_t upload(DevBuf& b, const std::vector<T>& h, const T*& field) {
   hipError_t e = b.alloc(h.size() * sizeof(T));
   if (e != hipSuccess) return e;
+  field = (const T*)b.p;
   if (!h.empty()) e = hipMemcpy(b.p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice);
   return e;
 }
@@ -128,32 +179,14 @@ struct p2v_verifier {
   int device = 0;
   size_t max_batch = 0, Bmax = 0;
   DevCircuit dc{};
-  std::vector<DevBuf> bufs;
   size_t in_bytes = 0;              // the host-input staging buffer `in`, allocated by the first run that needs it
                                     // (device-resident batches never do: a 131 072-proof workspace saves 16.6 GB)
-  DevBuf in, chal, leafdig, mk, fbits, qvals, van, vparts, lutre, lutpart, res, trace;
-  DevBuf m_plan, m_fol, m_chain, m_count, m_fix, m_badq, m_node;   // shared-node Merkle paths (dev.h mcse)
-  DevBuf t_cs, t_kis, t_gkind, t_gpar, t_ggrp, t_gwoff, t_w, t_gs, t_ge, t_lin, t_lout, t_loff, t_llen, t_tw, t_ops, t_vit, t_rin, t_rout, t_roff, t_rch, t_pbase, t_pw;
-  hipEvent_t ev[2 * kNumKernels];   // start/end per kernel
-  hipEvent_t dep_p1 = nullptr, dep_side = nullptr;
-  hipEvent_t p1_done = nullptr;      // recorded on the caller's stream after phase 1 (p2v_verifier_chain)
   std::atomic<bool> p1_recorded{false};   // read by the workspaces chained to this one, from their host threads
   p2v_verifier* chain_prev = nullptr;     // chain links: guarded by g_chain_mu
   std::vector<p2v_verifier*> chain_next;  // workspaces whose chain_prev is this one (cleared when this one is freed)
-  hipStream_t side = nullptr;
-  hipStream_t side2 = nullptr;      // small batches: k_fri beside the vanishing kernels (latency mode)
-  hipEvent_t dep_fri = nullptr;
-  // transcript lookahead (P2V_FLAG_LOOKAHEAD): its own stream, two challenge buffers used by
-  // alternate runs; tr_done[s]: the transcript into buffer s is complete, chal_free[s]: the run
-  // that read buffer s has completed (k_status)
-  hipStream_t ts = nullptr;
-  hipStream_t side3 = nullptr;      // latency mode: the coset / misc vanishing kernels beside the Poseidon parts
-  hipEvent_t dep_v3 = nullptr;
-  hipEvent_t tr_done[2] = {nullptr, nullptr}, chal_free[2] = {nullptr, nullptr};
-  DevBuf chal2;
   unsigned la_seq = 0;
   float last_ms[kNumKernels] = {0};
-  bool timed = false;
+  bool timed = false;               // all of ev[] exist: p2v_verifier_run records them
   int transcript_mode = 0;          // 0 auto, 1 row, 2 quad, 3 lane, 4 pair (env P2V_TRANSCRIPT)
   int quad_min_batch = 4096;        // auto: quad form from this batch size on (env P2V_QUAD_MIN); round 5: with the
                                     // latency row form (lposeidon.h) the row transcript wins up to 2048 proofs
@@ -166,21 +199,40 @@ struct p2v_verifier {
                                     // batch size (env P2V_LAT_MAX, measurement)
   bool single_stream = false;       // env P2V_SINGLE_STREAM=1: no side stream (measurement)
   bool debug_sync = false;          // env P2V_DEBUG_SYNC=1: name each launch on stderr and synchronise after it (fault isolation)
-  // JSON ingest on the device (p2v_verifier_run_json): the current template and its device
-  // form, and buffers grown on demand
+  // JSON ingest on the device (p2v_verifier_run_json): the current template and its device form
   ProofTemplate tmpl;
   bool have_tmpl = false;
   int64_t skel_len = 0, ntok = 0;
-  DevBuf j_blob, j_offs, j_skel, j_tok, j_ok;
   // binary-proof ingest (p2v_verifier_run_bytes): the circuit's byte map on the device, made once
-  DevBuf b_rsrc, b_rdst, b_rlen, b_coff, b_cval;
   bool have_bmap = false;
   int nruns = 0, nchk = 0;
   int64_t bfixed = 0;
+
+  // What the workspace owns on the device.  Members are destroyed in reverse order: the buffers
+  // first (hipFree waits for the device, so nothing is queued any more), then the streams, the
+  // events and the pinned memory.
   // pinned host staging for the small device->host results (statuses, JSON ok flags): a copy
   // to pageable memory would stage through the runtime and stall the other streams' work
-  int8_t* h_res = nullptr;
+  PinnedBuf h_res;
+  Event ev[2 * kNumKernels];        // start/end per kernel
+  Event dep_p1, dep_side, dep_fri, dep_v3;
+  Event p1_done;                    // recorded on the caller's stream after phase 1 (p2v_verifier_chain)
+  // transcript lookahead (P2V_FLAG_LOOKAHEAD): its own stream, two challenge buffers used by
+  // alternate runs; tr_done[s]: the transcript into buffer s is complete, chal_free[s]: the run
+  // that read buffer s has completed (k_status)
+  Event tr_done[2], chal_free[2];
+  Stream side;
+  Stream side2;                     // small batches: k_fri beside the vanishing kernels (latency mode)
+  Stream ts;                        // the lookahead transcript's
+  Stream side3;                     // latency mode: the coset / misc vanishing kernels beside the Poseidon parts
+  DevBuf in, chal, chal2, leafdig, mk, fbits, qvals, van, vparts, lutre, lutpart, res, trace;
+  DevBuf m_plan, m_fol, m_chain, m_count, m_fix, m_badq, m_node;   // shared-node Merkle paths (dev.h mcse)
+  DevBuf t_cs, t_kis, t_gkind, t_gpar, t_ggrp, t_gwoff, t_w, t_gs, t_ge, t_lin, t_lout, t_loff, t_llen, t_tw, t_ops, t_vit, t_rin, t_rout, t_roff, t_rch, t_pbase, t_pw;
+  DevBuf j_blob, j_offs, j_skel, j_tok, j_ok;          // JSON / binary ingest, grown on demand
+  DevBuf b_rsrc, b_rdst, b_rlen, b_coff, b_cval;       // the byte map
 };
+struct VerifierFree { void operator()(p2v_verifier* v) const { p2v_verifier_free(v); } };
+using VerifierPtr = std::unique_ptr<p2v_verifier, VerifierFree>;
 
 // One device's pipeline for batches in host memory (p2v_verify_batch / _devices): a verifier, a
 // compute stream and a copy stream, and a ring of kRing device chunk buffers, so chunk i+1's H2D
@@ -190,22 +242,21 @@ struct HostPipe {
   static constexpr int kRing = 3;
   int device = -1;
   size_t cap = 0;                 // the verifier's max_batch = the largest chunk
-  p2v_verifier* v = nullptr;
-  hipStream_t st = nullptr, cs = nullptr;
-  DevBuf ring[kRing];
-  hipEvent_t copied[kRing] = {}, freed[kRing] = {};
   bool have_ring = false;
-  DevBuf dres;                    // device statuses of the whole call (grown on demand)
-  int8_t* h_res = nullptr;        // pinned staging for them
-  size_t h_res_cap = 0;
-  // binary-proof ingest (p2v_verify_batch_bytes): per ring slot the chunk's bytes and offsets on
-  // the device, the offsets' host copy (rewritten once the slot's previous copy is done), and the
-  // device packer's ok flags of the whole call
-  DevBuf bbytes[kRing], boffs[kRing], dok;
   std::vector<uint64_t> hoffs[kRing];
-  int8_t* h_ok = nullptr;
-  size_t h_ok_cap = 0;
   bool busy = false;
+  // owned, destroyed in reverse order: the buffers, the events, the pinned memory, the streams
+  // and last the verifier (through p2v_verifier_free)
+  VerifierPtr v;
+  Stream st, cs;
+  PinnedBuf h_res, h_ok;          // pinned staging for dres and dok
+  Event copied[kRing], freed[kRing];
+  DevBuf ring[kRing];
+  DevBuf dres;                    // device statuses of the whole call (grown on demand)
+  // binary-proof ingest (p2v_verify_batch_bytes): per ring slot the chunk's bytes and offsets on
+  // the device, the offsets' host copy (hoffs, rewritten once the slot's previous copy is done),
+  // and the device packer's ok flags of the whole call
+  DevBuf bbytes[kRing], boffs[kRing], dok;
 };
 
 namespace {
@@ -214,22 +265,165 @@ void pipe_free(HostPipe* p) {
   (void)hipSetDevice(p->device);
   if (p->st) (void)hipStreamSynchronize(p->st);
   if (p->cs) (void)hipStreamSynchronize(p->cs);
-  for (int k = 0; k < HostPipe::kRing; k++) {
-    p->ring[k].free_();
-    if (p->copied[k]) (void)hipEventDestroy(p->copied[k]);
-    if (p->freed[k]) (void)hipEventDestroy(p->freed[k]);
-  }
-  p->dres.free_();
-  p->dok.free_();
-  for (int k = 0; k < HostPipe::kRing; k++) { p->bbytes[k].free_(); p->boffs[k].free_(); }
-  if (p->h_res) (void)hipHostFree(p->h_res);
-  if (p->h_ok) (void)hipHostFree(p->h_ok);
-  if (p->st) (void)hipStreamDestroy(p->st);
-  if (p->cs) (void)hipStreamDestroy(p->cs);
-  p2v_verifier_free(p->v);
   delete p;
 }
 constexpr int kPoolIdleMax = 4;   // idle pipes kept per (circuit, device)
+
+#define HCK_AS(what, x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { return fail(P2V_E_DEVICE, std::string(what) + ": " + hipGetErrorString(e_)); } } while (0)
+#define HCK(x) HCK_AS(#x, x)
+#define RCK(x) do { const int rc_ = (x); if (rc_ != P2V_OK) return rc_; } while (0)   // a P2V_* code passed on
+
+// ---- what p2v_verifier_create derives from the circuit, one function per table ----
+
+// the scalar and layout fields of DevCircuit, the unit orders, root powers and step shifts
+void fill_scalars(const Circuit& C, DevCircuit& d) {
+  d.r = C.r; d.Q = C.num_queries; d.S = (int)C.arities.size(); d.T = 4 + d.S;
+  d.num_pis = C.num_pis; d.cap_len = C.cap_len; d.degree_bits = C.degree_bits; d.lde_bits = C.lde_bits; d.pow_bits = C.pow_bits;
+  d.num_wires = C.num_wires; d.num_routed = C.num_routed; d.num_constants = C.num_constants; d.ngc = C.num_gate_consts;
+  d.ngroups = (int)C.grp_start.size(); d.nls = C.nls; d.nlp = C.nlp; d.npp = C.npp; d.qdf = C.qdf; d.nluts = (int)C.lut_in.size();
+  d.depth0 = C.depth0; d.final_len = C.final_len;
+  for (int t = 0; t < 4; t++) { d.width[t] = C.oracle_width[t]; d.lwidth[t] = C.leaf_width[t]; }
+  d.noop_leaves = C.noop_leaves ? 1 : 0;
+  d.n_gates = C.n_gate_eval; d.n_pp_terms = (int)C.n_pp_terms_per_round; d.n_lookup_terms = (int)C.n_lookup_terms_per_round;
+  d.alpha_base_gates = C.alpha_base_gates;
+  const Layout& L = C.L;
+  d.pis = L.pis; d.wcap = L.wcap; d.zcap = L.zcap; d.qcap = L.qcap; d.o_const = L.o_const; d.o_sig = L.o_sig; d.o_wires = L.o_wires;
+  d.o_zs = L.o_zs; d.o_pp = L.o_pp; d.o_quot = L.o_quot; d.o_lzs = L.o_lzs; d.o_zs_next = L.o_zs_next; d.o_lzs_next = L.o_lzs_next;
+  d.n_this = L.n_this; d.n_next = L.n_next; d.ccaps = L.ccaps; d.final_poly = L.final_poly; d.pow = L.pow; d.q0 = L.q0; d.qstride = L.qstride;
+  for (int t = 0; t < 4; t++) { d.leaf[t] = L.leaf[t]; d.path[t] = L.path[t]; }
+  {   // unit orders: most expensive tree first (stable), see DevCircuit::leaf_order
+    std::vector<std::pair<int64_t, int>> lc, mc;
+    for (int t = 0; t < d.T; t++) {
+      const int64_t len = t < 4 ? C.leaf_width[t] : (2ll << C.arities[t - 4]);
+      lc.push_back({-(len + 7) / 8, t});
+      mc.push_back({-(int64_t)(t < 4 ? C.depth0 : C.step_depth[t - 4]), t});
+    }
+    std::stable_sort(lc.begin(), lc.end()); std::stable_sort(mc.begin(), mc.end());
+    for (int k = 0; k < d.T; k++) { d.leaf_order[k] = (int8_t)lc[k].second; d.merkle_order[k] = (int8_t)mc[k].second; }
+  }
+  for (int s = 0; s < d.S; s++) { d.step_evals[s] = L.step_evals[s]; d.step_path[s] = L.step_path[s]; d.arity[s] = C.arities[s]; d.step_depth[s] = C.step_depth[s]; }
+  d.words = L.words;
+  for (int i = 0; i < 4; i++) d.digest[i] = C.digest[i];
+  { uint64_t x = gl::TWO_ADIC_GEN; for (int m = 0; m <= 32; m++) { d.root_pow2[m] = x; x = gl::mul(x, x); } }
+  {
+    uint64_t shift = gl::MULT_GEN; int logn = C.lde_bits;
+    for (int s = 0; s <= d.S; s++) {
+      d.step_shift[s] = shift; d.step_shift_inv[s] = gl::inv(shift);
+      if (s < d.S) { d.step_logn[s] = logn; d.inv_arity[s] = gl::inv(1ULL << C.arities[s]); shift = gl::pow(shift, 1ULL << C.arities[s]); logn -= C.arities[s]; }
+    }
+  }
+}
+
+// the gate and lookup tables
+struct CircuitTables {
+  std::vector<int32_t> gkind, ggrp, gwoff, gs, ge; std::vector<int64_t> gpar; std::vector<uint64_t> wts;
+  std::vector<uint64_t> lin, lout; std::vector<int64_t> loff, llen;
+  std::vector<uint32_t> rin, rout; std::vector<int64_t> roff; std::vector<int32_t> rch, pbase{0};
+};
+CircuitTables circuit_tables(const Circuit& C) {
+  CircuitTables t;
+  for (int g = 0; g < C.n_gate_eval; g++) {
+    const GateDesc& gd = C.gates[g];
+    t.gkind.push_back(gd.kind); t.ggrp.push_back(C.sel_idx[g]);
+    t.gpar.push_back(gd.p0); t.gpar.push_back(gd.p1); t.gpar.push_back(gd.p2);
+    t.gwoff.push_back((int32_t)t.wts.size()); t.wts.insert(t.wts.end(), gd.weights.begin(), gd.weights.end());
+  }
+  t.gwoff.push_back((int32_t)t.wts.size());
+  t.gs.assign(C.grp_start.begin(), C.grp_start.end()); t.ge.assign(C.grp_end.begin(), C.grp_end.end());
+  for (size_t k = 0; k < C.lut_in.size(); k++) {
+    t.loff.push_back((int64_t)t.lin.size()); t.llen.push_back((int64_t)C.lut_in[k].size());
+    t.lin.insert(t.lin.end(), C.lut_in[k].begin(), C.lut_in[k].end()); t.lout.insert(t.lout.end(), C.lut_out[k].begin(), C.lut_out[k].end());
+  }
+  // evalFinalRE (Lookups.hs:103-109): cur = sum_i delta^(N-1-i) (inp_i + B out_i) over the table
+  // padded to N = ceil(len / slots) * slots entries with its FIRST entry.  Stored reversed
+  // (index t = N-1-i is the power of delta) and zero-filled to a multiple of P2V_LUT_CHUNK, so
+  // the device evaluates it as sum_c delta^(16c) sum_j delta^j e'_(16c+j) (baby/giant steps).
+  const int64_t slots = C.num_routed / 3;
+  for (size_t k = 0; k < C.lut_in.size(); k++) {
+    const auto& li = C.lut_in[k]; const auto& lo = C.lut_out[k];
+    const int64_t len = (int64_t)li.size();
+    const int64_t N = slots > 0 ? (len + slots - 1) / slots * slots : 0;
+    bool small = len > 0;
+    for (int64_t i = 0; i < len && small; i++) small = li[i] < (1u << 24) && lo[i] < (1u << 24);
+    const int64_t nch = small ? (N + P2V_LUT_CHUNK - 1) / P2V_LUT_CHUNK : 0;
+    t.roff.push_back((int64_t)t.rin.size()); t.rch.push_back((int32_t)nch);
+    t.pbase.push_back(t.pbase.back() + (int32_t)((nch + P2V_LUT_PIECE - 1) / P2V_LUT_PIECE));
+    for (int64_t j = 0; j < nch * P2V_LUT_CHUNK; j++) {
+      const int64_t i = N - 1 - j, ii = i < len ? i : 0;
+      t.rin.push_back(j < N ? (uint32_t)li[ii] : 0u);
+      t.rout.push_back(j < N ? (uint32_t)lo[ii] : 0u);
+    }
+  }
+  return t;
+}
+
+std::vector<uint64_t> fri_twiddles(const Circuit& C) {
+  const int S = (int)C.arities.size();
+  std::vector<uint64_t> tw(256 * (size_t)(S ? S : 1), 0);
+  for (int s = 0; s < S; s++) {
+    int ab = C.arities[s];
+    uint64_t om_inv = gl::inv(gl::subgroup_gen(ab)), x = 1;
+    for (int j = 0; j < (1 << ab) && j < 256; j++) { tw[256 * s + j] = x; x = gl::mul(x, om_inv); }
+  }
+  return tw;
+}
+
+// transcript op program: proofChallenges (Challenge/Verifier.hs:58-103) + friChallenges (Challenge/FRI.hs:65-104);
+// d holds its scalars (fill_scalars) and receives ntops
+std::vector<int32_t> transcript_ops(const Circuit& C, DevCircuit& d) {
+  const Layout& L = C.L;
+  std::vector<int32_t> ops;
+  auto op = [&](int t, int64_t a_, int64_t n_) { ops.push_back(t); ops.push_back((int32_t)a_); ops.push_back((int32_t)n_); };
+  const int r = d.r, C4 = 4 * C.cap_len;
+  op(TOP_ABSORB_DIGEST, 0, 4);
+  op(TOP_ABSORB_PIH, 0, 4);
+  op(TOP_ABSORB_SOA, L.wcap, C4);
+  op(TOP_SQUEEZE, CH_BETA(d), r);
+  op(TOP_SQUEEZE, CH_GAMMA(d), r);
+  if (C.nlp > 0) { op(TOP_COPY, CH_DELTA(d), 2 * r); op(TOP_SQUEEZE, CH_DELTA(d) + 2 * r, 2 * r); }
+  else op(TOP_ZERO, CH_DELTA(d), 4 * r);
+  op(TOP_ABSORB_SOA, L.zcap, C4);
+  op(TOP_SQUEEZE, CH_ALPHA(d), r);
+  op(TOP_ABSORB_SOA, L.qcap, C4);
+  op(TOP_SQUEEZE, CH_ZETA(d), 2);
+  op(TOP_ABSORB_SOA, L.o_const, 2 * (L.n_this + L.n_next));
+  op(TOP_SQUEEZE, CH_FRI_ALPHA(d), 2);
+  for (int s = 0; s < d.S; s++) { op(TOP_ABSORB_SOA, L.ccaps + (int64_t)s * C4, C4); op(TOP_SQUEEZE, CH_FRI_BETA(d) + 2 * s, 2); }
+  op(TOP_ABSORB_SOA, L.final_poly, 2 * C.final_len);
+  op(TOP_ABSORB_SOA, L.pow, 1);
+  op(TOP_SQUEEZE, CH_POW(d), 1);
+  op(TOP_SQUEEZE_IDX, CH_QIDX(d), d.Q);
+  d.ntops = (int)(ops.size() / 3);
+  return ops;
+}
+
+// vanishing work items, heaviest first so their waves are dispatched first; d receives the
+// class bounds vcls and n_vitems
+std::vector<int32_t> vanish_items(const Circuit& C, DevCircuit& d) {
+  std::vector<int32_t> vit;
+  auto item = [&](int t, int a_, int b_, int64_t first) { vit.push_back(t); vit.push_back(a_); vit.push_back(b_); vit.push_back((int32_t)first); };
+  auto kind = [&](int g) { return C.gates[g].kind; };
+  d.vcls[0] = 0;
+  for (int g = 0; g < C.n_gate_eval; g++)
+    if (kind(g) == G_POSEIDON) for (int k = 0; k < P2V_POSEIDON_PARTS; k++) item(VI_GATE, g, k, p2v_poseidon_part_first_term(k));
+  d.vcls[1] = (int)(vit.size() / 4);
+  for (int g = 0; g < C.n_gate_eval; g++)   // one item per interpolation chunk (dev.h p2v_coset_parts)
+    if (kind(g) == G_COSET) {
+      const GateDesc& gd = C.gates[g];
+      const int64_t parts = p2v_coset_parts((int)gd.p0, gd.p1, (int32_t)gd.weights.size());
+      for (int64_t k = 0; k < parts; k++) item(VI_GATE, g, (int)k, p2v_coset_part_first_term(k));
+    }
+  d.vcls[2] = (int)(vit.size() / 4);
+  for (int g = 0; g < C.n_gate_eval; g++) if (kind(g) != G_POSEIDON && kind(g) != G_COSET) item(VI_GATE, g, 0, 0);
+  for (int j = 0; j < d.r; j++) item(VI_PP, j, 0, d.r + (int64_t)j * d.n_pp_terms);
+  item(VI_ZS1, 0, 0, 0);
+  d.vcls[3] = (int)(vit.size() / 4);
+  if (d.nluts > 0)
+    for (int j = 0; j < d.r; j++) item(VI_LOOKUP, j, 0, d.r + (int64_t)d.r * d.n_pp_terms + (int64_t)j * d.n_lookup_terms);
+  d.n_vitems = (int)(vit.size() / 4);
+  d.vcls[4] = d.n_vitems;
+  return vit;
+}
 }  // namespace
 
 p2v_circuit::~p2v_circuit() {
@@ -249,16 +443,13 @@ int p2v_circuit_from_json_ex(const char* common_json, size_t common_len, const c
                              p2v_circuit** out) {
   if (!common_json || !vkey_json || !out) return fail(P2V_E_ARG, "null argument");
   if (ext & ~P2V_EXT_PLONKY2) return fail(P2V_E_ARG, "unknown P2V_EXT_* flag");
-  try {
+  return guarded(P2V_E_PARSE, [&] {
     JVal cj = parse_json(common_json, common_len);
     JVal vj = parse_json(vkey_json, vkey_len);
-    auto* pc = new p2v_circuit();
-    try { pc->c = parse_circuit(cj, vj, ext); } catch (...) { delete pc; throw; }
-    *out = pc;
-    return P2V_OK;
-  } catch (const ParseError& e) { return fail(P2V_E_PARSE, e.what()); }
-  catch (const CircuitError& e) { return fail(P2V_E_CIRCUIT, e.what()); }
-  catch (const std::exception& e) { return fail(P2V_E_PARSE, e.what()); }
+    auto pc = std::make_unique<p2v_circuit>();
+    pc->c = parse_circuit(cj, vj, ext);
+    *out = pc.release();
+  });
 }
 
 int p2v_circuit_from_words(const uint64_t* words, size_t n, p2v_circuit** out) {
@@ -268,34 +459,21 @@ int p2v_circuit_from_words(const uint64_t* words, size_t n, p2v_circuit** out) {
 int p2v_circuit_from_words_ex(const uint64_t* words, size_t n, uint32_t ext, p2v_circuit** out) {
   if (!words || !out) return fail(P2V_E_ARG, "null argument");
   if (ext & ~P2V_EXT_PLONKY2) return fail(P2V_E_ARG, "unknown P2V_EXT_* flag");
-  try {
-    auto* pc = new p2v_circuit();
-    try { pc->c = parse_circuit_words(words, n, ext); } catch (...) { delete pc; throw; }
-    *out = pc;
-    return P2V_OK;
-  } catch (const ParseError& e) { return fail(P2V_E_PARSE, e.what()); }
-  catch (const CircuitError& e) { return fail(P2V_E_CIRCUIT, e.what()); }
-  catch (const std::exception& e) { return fail(P2V_E_PARSE, e.what()); }
+  return guarded(P2V_E_PARSE, [&] {
+    auto pc = std::make_unique<p2v_circuit>();
+    pc->c = parse_circuit_words(words, n, ext);
+    *out = pc.release();
+  });
 }
 
 int p2v_pack_proof_words(const p2v_circuit* pc, const uint64_t* words, size_t n, uint64_t* dst) {
   if (!pc || !words || !dst) return fail(P2V_E_ARG, "null argument");
-  try {
-    pack_proof_words(pc->c, words, n, dst);
-    return P2V_OK;
-  } catch (const ShapeError& e) { return fail(P2V_E_SHAPE, e.what()); }
-  catch (const ParseError& e) { return fail(P2V_E_PARSE, e.what()); }
-  catch (const std::exception& e) { return fail(P2V_E_PARSE, e.what()); }
+  return guarded(P2V_E_PARSE, [&] { pack_proof_words(pc->c, words, n, dst); });
 }
 
 int p2v_pack_proof_bytes(const p2v_circuit* pc, const uint8_t* bytes, size_t n, uint64_t* dst) {
   if (!pc || !bytes || !dst) return fail(P2V_E_ARG, "null argument");
-  try {
-    pack_proof_bytes(pc->c, bytes, n, dst);
-    return P2V_OK;
-  } catch (const ShapeError& e) { return fail(P2V_E_SHAPE, e.what()); }
-  catch (const ParseError& e) { return fail(P2V_E_PARSE, e.what()); }
-  catch (const std::exception& e) { return fail(P2V_E_PARSE, e.what()); }
+  return guarded(P2V_E_PARSE, [&] { pack_proof_bytes(pc->c, bytes, n, dst); });
 }
 
 void p2v_circuit_free(p2v_circuit* c) { delete c; }
@@ -318,13 +496,10 @@ int p2v_circuit_get_info(const p2v_circuit* pc, p2v_circuit_info* info) {
 
 int p2v_pack_proof_json(const p2v_circuit* pc, const char* proof_json, size_t len, uint64_t* dst) {
   if (!pc || !proof_json || !dst) return fail(P2V_E_ARG, "null argument");
-  try {
+  return guarded(P2V_E_PARSE, [&] {
     JVal pj = parse_json(proof_json, len);
     pack_proof(pc->c, pj, dst);
-    return P2V_OK;
-  } catch (const ShapeError& e) { return fail(P2V_E_SHAPE, e.what()); }
-  catch (const ParseError& e) { return fail(P2V_E_PARSE, e.what()); }
-  catch (const std::exception& e) { return fail(P2V_E_PARSE, e.what()); }
+  });
 }
 
 int p2v_proof_shape_json(const char* proof_json, size_t len, int* num_public_inputs, int* final_poly_len) {
@@ -346,13 +521,12 @@ int p2v_proof_shape_words(const uint64_t* words, size_t n, int* num_public_input
 int p2v_circuit_shape_variant(const p2v_circuit* pc, int num_public_inputs, int final_poly_len, p2v_circuit** out) {
   if (!pc || !out) return fail(P2V_E_ARG, "null argument");
   *out = nullptr;
-  try {
-    auto* v = new p2v_circuit();
+  try {   // its own mapping: a CircuitError here is the proof's shape past this build's limits
+    auto v = std::make_unique<p2v_circuit>();
     v->c = circuit_shape_variant(pc->c, num_public_inputs, final_poly_len);
-    *out = v;
+    *out = v.release();
     return P2V_OK;
-  } catch (const CircuitError& e) { return fail(P2V_E_SHAPE, e.what()); }
-  catch (const std::exception& e) { return fail(P2V_E_SHAPE, e.what()); }
+  } catch (const std::exception& e) { return fail(P2V_E_SHAPE, e.what()); }
 }
 
 int p2v_pack_proofs_json(const p2v_circuit* pc, const char* const* jsons, const size_t* lens, size_t n, uint64_t* dst,
@@ -367,7 +541,6 @@ int p2v_pack_proofs_json(const p2v_circuit* pc, const char* const* jsons, const 
       pack_proof(C, pj, dst + (size_t)W * i);
       return P2V_OK;
     } catch (const ShapeError& e) { if (msg) *msg = e.what(); return P2V_E_SHAPE; }
-    catch (const ParseError& e) { if (msg) *msg = e.what(); return P2V_E_PARSE; }
     catch (const std::exception& e) { if (msg) *msg = e.what(); return P2V_E_PARSE; }
   };
   // template from the first proof that packs
@@ -407,8 +580,6 @@ int p2v_device_count(void) {
   return n;
 }
 
-#define HCK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { return fail(P2V_E_DEVICE, std::string(#x) + ": " + hipGetErrorString(e_)); } } while (0)
-
 // the staging buffer for batches given in host memory (run from host, JSON / binary ingest)
 static hipError_t input_buf(p2v_verifier* v) {
   return v->in.p ? hipSuccess : v->in.alloc(v->in_bytes);
@@ -425,26 +596,6 @@ void p2v_verifier_free(p2v_verifier* v) {
     }
   }
   (void)hipSetDevice(v->device);
-  for (DevBuf* b : {&v->in, &v->chal, &v->leafdig, &v->mk, &v->fbits, &v->qvals, &v->van, &v->vparts, &v->lutre, &v->res, &v->trace, &v->t_cs, &v->t_kis,
-                    &v->t_gkind, &v->t_gpar, &v->t_ggrp, &v->t_gwoff, &v->t_w, &v->t_gs, &v->t_ge, &v->t_lin, &v->t_lout, &v->t_loff, &v->t_llen, &v->t_tw, &v->t_ops, &v->t_vit, &v->t_rin, &v->t_rout, &v->t_roff, &v->t_rch, &v->t_pbase, &v->t_pw, &v->lutpart, &v->chal2, &v->j_blob, &v->j_offs, &v->j_skel, &v->j_tok, &v->j_ok,
-                    &v->b_rsrc, &v->b_rdst, &v->b_rlen, &v->b_coff, &v->b_cval,
-                    &v->m_plan, &v->m_fol, &v->m_chain, &v->m_count, &v->m_fix, &v->m_badq, &v->m_node})
-    b->free_();
-  if (v->timed) for (auto& e : v->ev) (void)hipEventDestroy(e);
-  if (v->dep_p1) (void)hipEventDestroy(v->dep_p1);
-  if (v->dep_side) (void)hipEventDestroy(v->dep_side);
-  if (v->p1_done) (void)hipEventDestroy(v->p1_done);
-  if (v->side) (void)hipStreamDestroy(v->side);
-  if (v->side2) (void)hipStreamDestroy(v->side2);
-  if (v->ts) (void)hipStreamDestroy(v->ts);
-  if (v->side3) (void)hipStreamDestroy(v->side3);
-  if (v->dep_v3) (void)hipEventDestroy(v->dep_v3);
-  for (int k = 0; k < 2; k++) {
-    if (v->tr_done[k]) (void)hipEventDestroy(v->tr_done[k]);
-    if (v->chal_free[k]) (void)hipEventDestroy(v->chal_free[k]);
-  }
-  if (v->dep_fri) (void)hipEventDestroy(v->dep_fri);
-  if (v->h_res) (void)hipHostFree(v->h_res);
   delete v;
 }
 
@@ -468,7 +619,7 @@ int p2v_verifier_create(const p2v_circuit* pc, int device, size_t max_batch, p2v
   if (device < 0 || device >= ndev) return fail(P2V_E_ARG, "bad device index");
   HCK(hipSetDevice(device));
   const Circuit& C = pc->c;
-  auto* v = new p2v_verifier();
+  VerifierPtr v(new p2v_verifier());   // every early return below frees what was made so far
   v->circ = pc; v->device = device; v->max_batch = max_batch;
   v->Bmax = (max_batch + 63) / 64 * 64;
   if (const char* ss = getenv("P2V_SINGLE_STREAM")) v->single_stream = ss[0] == '1';
@@ -480,199 +631,68 @@ int p2v_verifier_create(const p2v_circuit* pc, int device, size_t max_batch, p2v
   if (const char* tm = getenv("P2V_TRANSCRIPT")) v->transcript_mode = !strcmp(tm, "row") ? 1 : !strcmp(tm, "quad") ? 2 : !strcmp(tm, "lane") ? 3 : !strcmp(tm, "pair") ? 4 : 0;
   DevCircuit& d = v->dc;
   memset(&d, 0, sizeof d);
-  d.r = C.r; d.Q = C.num_queries; d.S = (int)C.arities.size(); d.T = 4 + d.S;
-  d.num_pis = C.num_pis; d.cap_len = C.cap_len; d.degree_bits = C.degree_bits; d.lde_bits = C.lde_bits; d.pow_bits = C.pow_bits;
-  d.num_wires = C.num_wires; d.num_routed = C.num_routed; d.num_constants = C.num_constants; d.ngc = C.num_gate_consts;
-  d.ngroups = (int)C.grp_start.size(); d.nls = C.nls; d.nlp = C.nlp; d.npp = C.npp; d.qdf = C.qdf; d.nluts = (int)C.lut_in.size();
-  d.depth0 = C.depth0; d.final_len = C.final_len;
-  for (int t = 0; t < 4; t++) { d.width[t] = C.oracle_width[t]; d.lwidth[t] = C.leaf_width[t]; }
-  d.noop_leaves = C.noop_leaves ? 1 : 0;
-  d.n_gates = C.n_gate_eval; d.n_pp_terms = (int)C.n_pp_terms_per_round; d.n_lookup_terms = (int)C.n_lookup_terms_per_round;
-  d.alpha_base_gates = C.alpha_base_gates;
-  const Layout& L = C.L;
-  d.pis = L.pis; d.wcap = L.wcap; d.zcap = L.zcap; d.qcap = L.qcap; d.o_const = L.o_const; d.o_sig = L.o_sig; d.o_wires = L.o_wires;
-  d.o_zs = L.o_zs; d.o_pp = L.o_pp; d.o_quot = L.o_quot; d.o_lzs = L.o_lzs; d.o_zs_next = L.o_zs_next; d.o_lzs_next = L.o_lzs_next;
-  d.n_this = L.n_this; d.n_next = L.n_next; d.ccaps = L.ccaps; d.final_poly = L.final_poly; d.pow = L.pow; d.q0 = L.q0; d.qstride = L.qstride;
-  for (int t = 0; t < 4; t++) { d.leaf[t] = L.leaf[t]; d.path[t] = L.path[t]; }
-  {   // unit orders: most expensive tree first (stable), see DevCircuit::leaf_order
-    std::vector<std::pair<int64_t, int>> lc, mc;
-    for (int t = 0; t < d.T; t++) {
-      const int64_t len = t < 4 ? C.leaf_width[t] : (2ll << C.arities[t - 4]);
-      lc.push_back({-(len + 7) / 8, t});
-      mc.push_back({-(int64_t)(t < 4 ? C.depth0 : C.step_depth[t - 4]), t});
-    }
-    std::stable_sort(lc.begin(), lc.end()); std::stable_sort(mc.begin(), mc.end());
-    for (int k = 0; k < d.T; k++) { d.leaf_order[k] = (int8_t)lc[k].second; d.merkle_order[k] = (int8_t)mc[k].second; }
-  }
-  for (int s = 0; s < d.S; s++) { d.step_evals[s] = L.step_evals[s]; d.step_path[s] = L.step_path[s]; d.arity[s] = C.arities[s]; d.step_depth[s] = C.step_depth[s]; }
-  d.words = L.words;
-  for (int i = 0; i < 4; i++) d.digest[i] = C.digest[i];
-  { uint64_t x = gl::TWO_ADIC_GEN; for (int m = 0; m <= 32; m++) { d.root_pow2[m] = x; x = gl::mul(x, x); } }
-  {
-    uint64_t shift = gl::MULT_GEN; int logn = C.lde_bits;
-    for (int s = 0; s <= d.S; s++) {
-      d.step_shift[s] = shift; d.step_shift_inv[s] = gl::inv(shift);
-      if (s < d.S) { d.step_logn[s] = logn; d.inv_arity[s] = gl::inv(1ULL << C.arities[s]); shift = gl::pow(shift, 1ULL << C.arities[s]); logn -= C.arities[s]; }
-    }
-  }
-  // circuit tables
-  std::vector<int32_t> gkind, ggrp, gwoff; std::vector<int64_t> gpar; std::vector<uint64_t> wts;
-  for (int g = 0; g < C.n_gate_eval; g++) {
-    const GateDesc& gd = C.gates[g];
-    gkind.push_back(gd.kind); ggrp.push_back(C.sel_idx[g]);
-    gpar.push_back(gd.p0); gpar.push_back(gd.p1); gpar.push_back(gd.p2);
-    gwoff.push_back((int32_t)wts.size()); wts.insert(wts.end(), gd.weights.begin(), gd.weights.end());
-  }
-  gwoff.push_back((int32_t)wts.size());
-  std::vector<uint64_t> lin, lout; std::vector<int64_t> loff, llen;
-  for (size_t t = 0; t < C.lut_in.size(); t++) { loff.push_back((int64_t)lin.size()); llen.push_back((int64_t)C.lut_in[t].size()); lin.insert(lin.end(), C.lut_in[t].begin(), C.lut_in[t].end()); lout.insert(lout.end(), C.lut_out[t].begin(), C.lut_out[t].end()); }
-  // evalFinalRE (Lookups.hs:103-109): cur = sum_i delta^(N-1-i) (inp_i + B out_i) over the table
-  // padded to N = ceil(len / slots) * slots entries with its FIRST entry.  Stored reversed
-  // (index t = N-1-i is the power of delta) and zero-filled to a multiple of P2V_LUT_CHUNK, so
-  // the device evaluates it as sum_c delta^(16c) sum_j delta^j e'_(16c+j) (baby/giant steps).
-  std::vector<uint32_t> rin, rout; std::vector<int64_t> roff; std::vector<int32_t> rch, pbase{0};
-  {
-    const int64_t slots = C.num_routed / 3;
-    for (size_t t = 0; t < C.lut_in.size(); t++) {
-      const auto& li = C.lut_in[t]; const auto& lo = C.lut_out[t];
-      const int64_t len = (int64_t)li.size();
-      const int64_t N = slots > 0 ? (len + slots - 1) / slots * slots : 0;
-      bool small = len > 0;
-      for (int64_t i = 0; i < len && small; i++) small = li[i] < (1u << 24) && lo[i] < (1u << 24);
-      const int64_t nch = small ? (N + P2V_LUT_CHUNK - 1) / P2V_LUT_CHUNK : 0;
-      roff.push_back((int64_t)rin.size()); rch.push_back((int32_t)nch);
-      pbase.push_back(pbase.back() + (int32_t)((nch + P2V_LUT_PIECE - 1) / P2V_LUT_PIECE));
-      for (int64_t k = 0; k < nch * P2V_LUT_CHUNK; k++) {
-        const int64_t i = N - 1 - k, ii = i < len ? i : 0;
-        rin.push_back(k < N ? (uint32_t)li[ii] : 0u);
-        rout.push_back(k < N ? (uint32_t)lo[ii] : 0u);
-      }
-    }
-  }
-  std::vector<uint64_t> tw(256 * (size_t)(d.S ? d.S : 1), 0);
-  for (int s = 0; s < d.S; s++) {
-    int ab = C.arities[s];
-    uint64_t om_inv = gl::inv(gl::subgroup_gen(ab)), x = 1;
-    for (int j = 0; j < (1 << ab) && j < 256; j++) { tw[256 * s + j] = x; x = gl::mul(x, om_inv); }
-  }
-  std::vector<int32_t> gs(C.grp_start.begin(), C.grp_start.end()), ge(C.grp_end.begin(), C.grp_end.end());
-  // transcript op program: proofChallenges (Challenge/Verifier.hs:58-103) + friChallenges (Challenge/FRI.hs:65-104)
-  std::vector<int32_t> ops;
-  auto op = [&](int t, int64_t a_, int64_t n_) { ops.push_back(t); ops.push_back((int32_t)a_); ops.push_back((int32_t)n_); };
-  {
-    const int r = d.r, C4 = 4 * C.cap_len;
-    op(TOP_ABSORB_DIGEST, 0, 4);
-    op(TOP_ABSORB_PIH, 0, 4);
-    op(TOP_ABSORB_SOA, L.wcap, C4);
-    op(TOP_SQUEEZE, CH_BETA(d), r);
-    op(TOP_SQUEEZE, CH_GAMMA(d), r);
-    if (C.nlp > 0) { op(TOP_COPY, CH_DELTA(d), 2 * r); op(TOP_SQUEEZE, CH_DELTA(d) + 2 * r, 2 * r); }
-    else op(TOP_ZERO, CH_DELTA(d), 4 * r);
-    op(TOP_ABSORB_SOA, L.zcap, C4);
-    op(TOP_SQUEEZE, CH_ALPHA(d), r);
-    op(TOP_ABSORB_SOA, L.qcap, C4);
-    op(TOP_SQUEEZE, CH_ZETA(d), 2);
-    op(TOP_ABSORB_SOA, L.o_const, 2 * (L.n_this + L.n_next));
-    op(TOP_SQUEEZE, CH_FRI_ALPHA(d), 2);
-    for (int s = 0; s < d.S; s++) { op(TOP_ABSORB_SOA, L.ccaps + (int64_t)s * C4, C4); op(TOP_SQUEEZE, CH_FRI_BETA(d) + 2 * s, 2); }
-    op(TOP_ABSORB_SOA, L.final_poly, 2 * C.final_len);
-    op(TOP_ABSORB_SOA, L.pow, 1);
-    op(TOP_SQUEEZE, CH_POW(d), 1);
-    op(TOP_SQUEEZE_IDX, CH_QIDX(d), d.Q);
-  }
-  d.ntops = (int)(ops.size() / 3);
-  // vanishing work items, heaviest first so their waves are dispatched first
-  std::vector<int32_t> vit;
-  {
-    auto item = [&](int t, int a_, int b_, int64_t first) { vit.push_back(t); vit.push_back(a_); vit.push_back(b_); vit.push_back((int32_t)first); };
-    d.vcls[0] = 0;
-    for (int g = 0; g < C.n_gate_eval; g++)
-      if (gkind[g] == G_POSEIDON) for (int k = 0; k < P2V_POSEIDON_PARTS; k++) item(VI_GATE, g, k, p2v_poseidon_part_first_term(k));
-    d.vcls[1] = (int)(vit.size() / 4);
-    for (int g = 0; g < C.n_gate_eval; g++)   // one item per interpolation chunk (dev.h p2v_coset_parts)
-      if (gkind[g] == G_COSET) {
-        const int64_t parts = p2v_coset_parts((int)gpar[3 * g], gpar[3 * g + 1], gwoff[g + 1] - gwoff[g]);
-        for (int64_t k = 0; k < parts; k++) item(VI_GATE, g, (int)k, p2v_coset_part_first_term(k));
-      }
-    d.vcls[2] = (int)(vit.size() / 4);
-    for (int g = 0; g < C.n_gate_eval; g++) if (gkind[g] != G_POSEIDON && gkind[g] != G_COSET) item(VI_GATE, g, 0, 0);
-    for (int j = 0; j < d.r; j++) item(VI_PP, j, 0, d.r + (int64_t)j * d.n_pp_terms);
-    item(VI_ZS1, 0, 0, 0);
-    d.vcls[3] = (int)(vit.size() / 4);
-    if (d.nluts > 0)
-      for (int j = 0; j < d.r; j++) item(VI_LOOKUP, j, 0, d.r + (int64_t)d.r * d.n_pp_terms + (int64_t)j * d.n_lookup_terms);
-  }
-  d.n_vitems = (int)(vit.size() / 4);
-  d.vcls[4] = d.n_vitems;
-  hipError_t e = hipSuccess;
-#define UP(buf, vec) if (e == hipSuccess) e = upload(buf, vec)
-  UP(v->t_cs, C.cs_cap); UP(v->t_kis, C.k_is); UP(v->t_gkind, gkind); UP(v->t_gpar, gpar); UP(v->t_ggrp, ggrp); UP(v->t_gwoff, gwoff);
-  UP(v->t_w, wts); UP(v->t_gs, gs); UP(v->t_ge, ge); UP(v->t_lin, lin); UP(v->t_lout, lout); UP(v->t_loff, loff); UP(v->t_llen, llen); UP(v->t_tw, tw); UP(v->t_ops, ops); UP(v->t_vit, vit);
-  UP(v->t_rin, rin); UP(v->t_rout, rout); UP(v->t_roff, roff); UP(v->t_rch, rch); UP(v->t_pbase, pbase);
-  UP(v->t_pw, poseidon_part3_table());
-  d.n_lut_pieces = pbase.back();
-#undef UP
+  fill_scalars(C, d);
+  const CircuitTables t = circuit_tables(C);
+  d.n_lut_pieces = t.pbase.back();
+#define ACK(x) HCK_AS("device allocation", x)
+  ACK(upload(v->t_cs, C.cs_cap, d.cs_cap)); ACK(upload(v->t_kis, C.k_is, d.k_is));
+  ACK(upload(v->t_gkind, t.gkind, d.gate_kind)); ACK(upload(v->t_gpar, t.gpar, d.gate_par)); ACK(upload(v->t_ggrp, t.ggrp, d.gate_grp));
+  ACK(upload(v->t_gwoff, t.gwoff, d.gate_woff)); ACK(upload(v->t_w, t.wts, d.weights)); ACK(upload(v->t_gs, t.gs, d.grp_start)); ACK(upload(v->t_ge, t.ge, d.grp_end));
+  ACK(upload(v->t_lin, t.lin, d.lut_in)); ACK(upload(v->t_lout, t.lout, d.lut_out)); ACK(upload(v->t_loff, t.loff, d.lut_off)); ACK(upload(v->t_llen, t.llen, d.lut_len));
+  ACK(upload(v->t_tw, fri_twiddles(C), d.twiddles)); ACK(upload(v->t_ops, transcript_ops(C, d), d.tops)); ACK(upload(v->t_vit, vanish_items(C, d), d.vitems));
+  ACK(upload(v->t_rin, t.rin, d.lut_rin)); ACK(upload(v->t_rout, t.rout, d.lut_rout)); ACK(upload(v->t_roff, t.roff, d.lut_roff));
+  ACK(upload(v->t_rch, t.rch, d.lut_rchunks)); ACK(upload(v->t_pbase, t.pbase, d.lut_pbase));
+  ACK(upload(v->t_pw, poseidon_part3_table(), d.pos_w));
   const size_t B = v->Bmax;
   const size_t chw = (size_t)(4 + 7 * d.r + 4 + 2 * d.S + 1 + d.Q + 4);
-  v->in_bytes = (size_t)L.words * v->Bmax * 8;   // whole 64-proof tiles (P2V_FLAG_INPUT_TILED); allocated on first use
-  if (e == hipSuccess) e = v->chal.alloc(chw * B * 8);
-  if (e == hipSuccess) e = v->chal2.alloc(chw * B * 8);
-  if (e == hipSuccess) e = v->leafdig.alloc((size_t)d.Q * d.T * 4 * B * 8);
-  if (e == hipSuccess) e = v->mk.alloc((size_t)d.Q * d.T * B);
-  if (e == hipSuccess) e = v->fbits.alloc((size_t)d.Q * B * 4);
-  if (e == hipSuccess) e = v->qvals.alloc((size_t)d.Q * 6 * B * 8);
-  if (e == hipSuccess) e = v->van.alloc((size_t)(1 + 4 * d.r) * B * 8);
-  if (e == hipSuccess) e = v->vparts.alloc((size_t)d.n_vitems * 2 * d.r * B * 8);
-  if (e == hipSuccess) e = v->lutre.alloc((size_t)d.r * (d.nluts ? d.nluts : 1) * B * 8);
-  if (e == hipSuccess) e = v->lutpart.alloc((size_t)d.r * (d.n_lut_pieces ? d.n_lut_pieces : 1) * B * 8);
-  if (e == hipSuccess) e = v->res.alloc(B);
-  if (e == hipSuccess) e = hipHostMalloc((void**)&v->h_res, B);
-  if (e == hipSuccess) e = v->trace.alloc((size_t)C.trace_words * B * 8);
+  v->in_bytes = (size_t)C.L.words * v->Bmax * 8;   // whole 64-proof tiles (P2V_FLAG_INPUT_TILED); allocated on first use
+  ACK(v->chal.alloc(chw * B * 8));
+  ACK(v->chal2.alloc(chw * B * 8));
+  ACK(v->leafdig.alloc((size_t)d.Q * d.T * 4 * B * 8));
+  ACK(v->mk.alloc((size_t)d.Q * d.T * B));
+  ACK(v->fbits.alloc((size_t)d.Q * B * 4));
+  ACK(v->qvals.alloc((size_t)d.Q * 6 * B * 8));
+  ACK(v->van.alloc((size_t)(1 + 4 * d.r) * B * 8));
+  ACK(v->vparts.alloc((size_t)d.n_vitems * 2 * d.r * B * 8));
+  ACK(v->lutre.alloc((size_t)d.r * (d.nluts ? d.nluts : 1) * B * 8));
+  ACK(v->lutpart.alloc((size_t)d.r * (d.n_lut_pieces ? d.n_lut_pieces : 1) * B * 8));
+  ACK(v->res.alloc(B));
+  ACK(v->h_res.grow(B));
+  ACK(v->trace.alloc((size_t)C.trace_words * B * 8));
   // shared-node Merkle paths: on unless P2V_MERKLE_CSE=0 or the shape exceeds the plan's fields
   d.mcse = v->merkle_cse && d.Q <= P2V_CSE_MAX_Q && d.depth0 <= P2V_CSE_MAX_DEPTH && B <= (size_t)P2V_CSE_MAX_B && d.T < 32;
   if (d.mcse) {
     const size_t ncls = 1 + (size_t)d.S, nb = 1 + (size_t)d.depth0;
     d.mcap = (int64_t)d.T * d.Q * (int64_t)B;
-    if (e == hipSuccess) e = v->m_plan.alloc(ncls * d.Q * B * 4);
-    if (e == hipSuccess) e = v->m_fol.alloc(ncls * d.Q * B * 8);
-    if (e == hipSuccess) e = v->m_chain.alloc(nb * (size_t)d.mcap * 4);
+    ACK(v->m_plan.alloc(ncls * d.Q * B * 4));
+    ACK(v->m_fol.alloc(ncls * d.Q * B * 8));
+    ACK(v->m_chain.alloc(nb * (size_t)d.mcap * 4));
     const size_t cnt_bytes = (nb + 1) * 64;   // bucket counters and the fix-list length, 64 B apart
-    if (e == hipSuccess) e = v->m_count.alloc(cnt_bytes);
-    if (e == hipSuccess) e = hipMemset(v->m_count.p, 0, cnt_bytes);   // then zeroed by each run's k_merkle_resolve
-    if (e == hipSuccess) e = v->m_fix.alloc((size_t)d.mcap * 4);
-    if (e == hipSuccess) e = v->m_badq.alloc((size_t)d.T * d.Q * B);
-    if (e == hipSuccess) e = v->m_node.alloc((size_t)d.T * d.Q * 4 * B * 8);
+    ACK(v->m_count.alloc(cnt_bytes));
+    ACK(hipMemset(v->m_count.p, 0, cnt_bytes));   // then zeroed by each run's k_merkle_resolve
+    ACK(v->m_fix.alloc((size_t)d.mcap * 4));
+    ACK(v->m_badq.alloc((size_t)d.T * d.Q * B));
+    ACK(v->m_node.alloc((size_t)d.T * d.Q * 4 * B * 8));
     d.mplan = (uint32_t*)v->m_plan.p; d.mfol = (uint64_t*)v->m_fol.p; d.mchain = (uint32_t*)v->m_chain.p;
     d.mcount = (int32_t*)v->m_count.p; d.mfixn = d.mcount + nb * 16; d.mfix = (uint32_t*)v->m_fix.p;
     d.mbadq = (uint8_t*)v->m_badq.p; d.mnode = (uint64_t*)v->m_node.p;
   }
-  if (e == hipSuccess) { for (auto& x : v->ev) { e = hipEventCreate(&x); if (e != hipSuccess) break; } v->timed = e == hipSuccess; }
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&v->dep_p1, hipEventDisableTiming);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&v->dep_side, hipEventDisableTiming);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&v->p1_done, hipEventDisableTiming);
+  for (Event& x : v->ev) ACK(x.create_timed());
+  v->timed = true;
+  ACK(v->dep_p1.create()); ACK(v->dep_side.create()); ACK(v->p1_done.create());
   // the side stream carries few, long-latency waves (vanishing items, FRI queries), at the default
   // priority (a high-priority queue changed nothing: DESIGN.md "Retired run-time switches")
-  if (e == hipSuccess) e = hipStreamCreateWithFlags(&v->side, hipStreamNonBlocking);
+  ACK(v->side.create());
   // (the latency-mode and lookahead streams are created on first use: every stream a process
   // creates may take one of its few hardware queues, GPU_MAX_HW_QUEUES = 4, and two workspaces'
   // main and side streams must not share one)
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&v->dep_v3, hipEventDisableTiming);
-  for (int k = 0; k < 2 && e == hipSuccess; k++) {
-    e = hipEventCreateWithFlags(&v->tr_done[k], hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&v->chal_free[k], hipEventDisableTiming);
-  }
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&v->dep_fri, hipEventDisableTiming);
-  if (e != hipSuccess) { p2v_verifier_free(v); return fail(P2V_E_DEVICE, std::string("device allocation: ") + hipGetErrorString(e)); }
-  d.cs_cap = (const uint64_t*)v->t_cs.p; d.k_is = (const uint64_t*)v->t_kis.p; d.gate_kind = (const int32_t*)v->t_gkind.p;
-  d.gate_par = (const int64_t*)v->t_gpar.p; d.gate_grp = (const int32_t*)v->t_ggrp.p; d.gate_woff = (const int32_t*)v->t_gwoff.p;
-  d.weights = (const uint64_t*)v->t_w.p; d.grp_start = (const int32_t*)v->t_gs.p; d.grp_end = (const int32_t*)v->t_ge.p;
-  d.lut_in = (const uint64_t*)v->t_lin.p; d.lut_out = (const uint64_t*)v->t_lout.p; d.lut_off = (const int64_t*)v->t_loff.p; d.lut_len = (const int64_t*)v->t_llen.p;
-  d.lut_rin = (const uint32_t*)v->t_rin.p; d.lut_rout = (const uint32_t*)v->t_rout.p; d.lut_roff = (const int64_t*)v->t_roff.p; d.lut_rchunks = (const int32_t*)v->t_rch.p; d.lut_pbase = (const int32_t*)v->t_pbase.p;
-  d.twiddles = (const uint64_t*)v->t_tw.p; d.tops = (const int32_t*)v->t_ops.p; d.vitems = (const int32_t*)v->t_vit.p;
-  d.pos_w = (const uint64_t*)v->t_pw.p;
+  ACK(v->dep_v3.create());
+  for (int k = 0; k < 2; k++) { ACK(v->tr_done[k].create()); ACK(v->chal_free[k].create()); }
+  ACK(v->dep_fri.create());
+#undef ACK
   d.chal = (uint64_t*)v->chal.p; d.leafdig = (uint64_t*)v->leafdig.p; d.mk_ok = (uint8_t*)v->mk.p;
   d.fri_bits = (uint32_t*)v->fbits.p; d.qvals = (uint64_t*)v->qvals.p; d.van = (uint64_t*)v->van.p; d.vparts = (uint64_t*)v->vparts.p; d.lutre = (uint64_t*)v->lutre.p; d.lutpart = (uint64_t*)v->lutpart.p;
-  *out = v;
+  *out = v.release();
   return P2V_OK;
 }
 
@@ -701,6 +721,10 @@ static void launch_transcript(const DevCircuit& d, int tl, int nt_blocks, hipStr
   auto* k = tl == 1 ? k_transcript_lane : tl == 2 ? k_transcript_pair : k_transcript;
   k<<<nt_blocks, 256, 0, s>>>(d, tl);
 }
+// one class of vanishing items, [first, last) of d.vitems: one wave per item and 64-proof tile
+static void launch_vanish(void (*k)(DevCircuit), int first, int last, int NPB, hipStream_t s, const DevCircuit& d) {
+  k<<<(last - first) * NPB, 64, 0, s>>>(d);
+}
 
 int p2v_verifier_run(p2v_verifier* v, const uint64_t* proofs, size_t n, int8_t* results, uint64_t* trace, void* stream_, uint32_t flags) {
   if (!v || (!proofs && n) || !results) return fail(P2V_E_ARG, "null argument");
@@ -728,7 +752,7 @@ int p2v_verifier_run(p2v_verifier* v, const uint64_t* proofs, size_t n, int8_t* 
   if (trace) dtrace = (flags & P2V_FLAG_RESULT_DEVICE) ? trace : (uint64_t*)v->trace.p;
   const int NPB = d.B / 64;
   const bool tm = v->timed;
-  hipStream_t sd = v->single_stream ? st : v->side;
+  hipStream_t sd = v->single_stream ? st : (hipStream_t)v->side;
   uint32_t timed_mask = 0;   // slots recorded in this run (only those are read back)
 #define T0(k, s_) do { if (tm) { HCK(hipEventRecord(v->ev[2 * (k)], s_)); timed_mask |= 1u << (k); } } while (0)
 #define T1(k, s_) do { if (tm) HCK(hipEventRecord(v->ev[2 * (k) + 1], s_)); } while (0)
@@ -765,27 +789,27 @@ int p2v_verifier_run(p2v_verifier* v, const uint64_t* proofs, size_t n, int8_t* 
   const bool la = (flags & P2V_FLAG_LOOKAHEAD) && (flags & P2V_FLAG_INPUT_DEVICE) && sd != st && !chained;
   int la_slot = 0;
   if (la) {
-    if (!v->ts) HCK(hipStreamCreateWithFlags(&v->ts, hipStreamNonBlocking));
+    if (!v->ts) HCK(v->ts.create());
     la_slot = (int)(v->la_seq++ & 1u);
     d.chal = (uint64_t*)(la_slot ? v->chal2.p : v->chal.p);
     HCK(hipStreamWaitEvent(v->ts, v->chal_free[la_slot], 0));
-    T0(9, v->ts);
+    T0(SLOT_TRANSCRIPT, v->ts);
     launch_transcript(d, tl, nt_blocks, v->ts);
     DBG("k_transcript", v->ts);
-    T1(9, v->ts);
+    T1(SLOT_TRANSCRIPT, v->ts);
     HCK(hipEventRecord(v->tr_done[la_slot], v->ts));
-    T0(8, st);
+    T0(SLOT_LEAF, st);
     k_leaf<<<(leaf_units + 3) / 4, 256, 0, st>>>(d);
     DBG("k_leaf", st);
-    T1(8, st);
+    T1(SLOT_LEAF, st);
     HCK(hipStreamWaitEvent(st, v->tr_done[la_slot], 0));   // k_merkle reads the query indices
     HCK(hipEventRecord(v->dep_p1, st));                     // the side kernels read the challenges
     HCK(hipStreamWaitEvent(sd, v->dep_p1, 0));
   } else {
-    T0(1, st);
+    T0(SLOT_PHASE1, st);
     launch_phase1(d, tl, nt_blocks, (leaf_units + 3) / 4, st);
     DBG("k_phase1", st);
-    T1(1, st);
+    T1(SLOT_PHASE1, st);
     if (sd != st) {
       HCK(hipEventRecord(v->dep_p1, st));
       HCK(hipStreamWaitEvent(sd, v->dep_p1, 0));
@@ -800,68 +824,58 @@ int p2v_verifier_run(p2v_verifier* v, const uint64_t* proofs, size_t n, int8_t* 
   const bool lat = d.n <= v->lat_max_batch;
   const int mk_wg = lat ? 64 : 256;
   const bool fri2 = lat && sd != st;
-  if (fri2 && !v->side2) HCK(hipStreamCreateWithFlags(&v->side2, hipStreamNonBlocking));
+  if (fri2 && !v->side2) HCK(v->side2.create());
   if (fri2) {
     HCK(hipStreamWaitEvent(v->side2, v->p1_done, 0));
-    T0(3, v->side2);
+    T0(SLOT_FRI, v->side2);
     k_fri<<<(d.Q * NPB * 64 + mk_wg - 1) / mk_wg, mk_wg, 0, v->side2>>>(d);
     DBG("k_fri", v->side2);
-    T1(3, v->side2);
+    T1(SLOT_FRI, v->side2);
     HCK(hipEventRecord(v->dep_fri, v->side2));
   }
   // phase 2: Merkle paths on the main stream; FRI queries and the vanishing kernel (few,
   // long-latency waves) on the side stream, concurrently
-  T0(7, sd);
+  T0(SLOT_LUT, sd);
   if (d.n_lut_pieces > 0) k_lut<<<(d.r * d.n_lut_pieces * NPB + 3) / 4, 256, 0, sd>>>(d);
   DBG("k_lut", sd);
-  T1(7, sd);
+  T1(SLOT_LUT, sd);
   // the vanishing items in three kernels (register allocation per class), timed together
-  T0(4, sd);
+  T0(SLOT_VANISH, sd);
   // (one wave per work-group; the _r2 forms hold exactly the standard 2 challenge rounds)
   const bool r2 = d.r == 2;
   // latency mode: the coset and misc items on a stream of their own, beside the Poseidon parts
   // (each class is a handful of waves whose chain is the batch's tail)
   hipStream_t sv = sd;
   if (fri2) {
-    if (!v->side3) HCK(hipStreamCreateWithFlags(&v->side3, hipStreamNonBlocking));
+    if (!v->side3) HCK(v->side3.create());
     HCK(hipStreamWaitEvent(v->side3, v->p1_done, 0));
     sv = v->side3;
   }
-  if (d.vcls[1] > d.vcls[0]) {
-    if (r2) k_vanish_poseidon_r2<<<(d.vcls[1] - d.vcls[0]) * NPB, 64, 0, sd>>>(d);
-    else k_vanish_poseidon_rn<<<(d.vcls[1] - d.vcls[0]) * NPB, 64, 0, sd>>>(d);
-  }
+  if (d.vcls[1] > d.vcls[0]) launch_vanish(r2 ? k_vanish_poseidon_r2 : k_vanish_poseidon_rn, d.vcls[0], d.vcls[1], NPB, sd, d);
   DBG("k_vanish_poseidon", sd);
-  if (d.vcls[2] > d.vcls[1]) {
-    if (r2) k_vanish_coset_r2<<<(d.vcls[2] - d.vcls[1]) * NPB, 64, 0, sv>>>(d);
-    else k_vanish_coset_rn<<<(d.vcls[2] - d.vcls[1]) * NPB, 64, 0, sv>>>(d);
-  }
+  if (d.vcls[2] > d.vcls[1]) launch_vanish(r2 ? k_vanish_coset_r2 : k_vanish_coset_rn, d.vcls[1], d.vcls[2], NPB, sv, d);
   DBG("k_vanish_coset", sv);
-  if (r2) k_vanish_r2<<<(d.vcls[3] - d.vcls[2]) * NPB, 64, 0, sv>>>(d);
-  else k_vanish_rn<<<(d.vcls[3] - d.vcls[2]) * NPB, 64, 0, sv>>>(d);
+  launch_vanish(r2 ? k_vanish_r2 : k_vanish_rn, d.vcls[2], d.vcls[3], NPB, sv, d);   // never empty: the Z(1) item
   DBG("k_vanish", sv);
   if (sv != sd) {
     HCK(hipEventRecord(v->dep_v3, sv));
     HCK(hipStreamWaitEvent(sd, v->dep_v3, 0));   // k_vanish_final sums every item
   }
-  if (d.vcls[4] > d.vcls[3]) {
-    if (r2) k_vanish_lookup_r2<<<(d.vcls[4] - d.vcls[3]) * NPB, 64, 0, sd>>>(d);
-    else k_vanish_lookup_rn<<<(d.vcls[4] - d.vcls[3]) * NPB, 64, 0, sd>>>(d);
-  }
+  if (d.vcls[4] > d.vcls[3]) launch_vanish(r2 ? k_vanish_lookup_r2 : k_vanish_lookup_rn, d.vcls[3], d.vcls[4], NPB, sd, d);
   DBG("k_vanish_lookup", sd);
-  T1(4, sd);
-  T0(6, sd);
+  T1(SLOT_VANISH, sd);
+  T0(SLOT_VANISH_FINAL, sd);
   k_vanish_final<<<(d.B + 255) / 256, 256, 0, sd>>>(d);
   DBG("k_vanish_final", sd);
-  T1(6, sd);
+  T1(SLOT_VANISH_FINAL, sd);
   if (!fri2) {   // after the vanishing kernels (before them: pipelined -1.5 %, DESIGN.md "Retired run-time switches")
-    T0(3, sd);
+    T0(SLOT_FRI, sd);
     k_fri<<<(d.Q * NPB * 64 + 255) / 256, 256, 0, sd>>>(d);
     DBG("k_fri", sd);
-    T1(3, sd);
+    T1(SLOT_FRI, sd);
   }
   if (sd != st) HCK(hipEventRecord(v->dep_side, sd));
-  T0(2, st);
+  T0(SLOT_MERKLE, st);
   const int merkle_units = d.Q * d.T * NPB;
   if (lat) k_merkle_row<<<(unsigned)(((int64_t)d.Q * d.T * d.n * 16 + 255) / 256), 256, 0, st>>>(d);
   else if (d.mcse) {
@@ -887,13 +901,13 @@ int p2v_verifier_run(p2v_verifier* v, const uint64_t* proofs, size_t n, int8_t* 
     v->cse_dirty = false;
   } else k_merkle<<<(merkle_units + 3) / 4, 256, 0, st>>>(d);
   DBG("k_merkle", st);
-  T1(2, st);
+  T1(SLOT_MERKLE, st);
   if (sd != st) HCK(hipStreamWaitEvent(st, v->dep_side, 0));
   if (fri2) HCK(hipStreamWaitEvent(st, v->dep_fri, 0));
-  T0(5, st);
+  T0(SLOT_STATUS, st);
   k_status<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(d, dres, dtrace, C.trace_words);
   DBG("k_status", st);
-  T1(5, st);
+  T1(SLOT_STATUS, st);
   // the challenge buffer's last reader is done (a run without the flag used buffer 0: a later
   // lookahead transcript into buffer 0 must wait for it as well)
   if (la) HCK(hipEventRecord(v->chal_free[la_slot], st));
@@ -903,12 +917,12 @@ int p2v_verifier_run(p2v_verifier* v, const uint64_t* proofs, size_t n, int8_t* 
 #undef DBG
   HCK(hipGetLastError());
   if (!(flags & P2V_FLAG_RESULT_DEVICE)) {
-    HCK(hipMemcpyAsync(v->h_res, dres, n, hipMemcpyDeviceToHost, st));
+    HCK(hipMemcpyAsync(v->h_res.p, dres, n, hipMemcpyDeviceToHost, st));
     if (trace) HCK(hipMemcpyAsync(trace, dtrace, (size_t)C.trace_words * n * 8, hipMemcpyDeviceToHost, st));
   }
   if (!(flags & P2V_FLAG_NO_SYNC) || !(flags & P2V_FLAG_RESULT_DEVICE)) {
     HCK(hipStreamSynchronize(st));
-    if (!(flags & P2V_FLAG_RESULT_DEVICE)) memcpy(results, v->h_res, n);
+    if (!(flags & P2V_FLAG_RESULT_DEVICE)) memcpy(results, v->h_res.p, n);
     if (tm) {
       for (int k = 0; k < kNumKernels; k++) {
         float ms = 0;
@@ -935,10 +949,11 @@ static int pipe_acquire(const p2v_circuit* c, int device, size_t cap, HostPipe**
   auto* p = new HostPipe();
   p->device = device; p->cap = cap;
   int rc = P2V_OK;
-  if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&p->st, hipStreamNonBlocking) != hipSuccess ||
-      hipStreamCreateWithFlags(&p->cs, hipStreamNonBlocking) != hipSuccess)
+  if (hipSetDevice(device) != hipSuccess || p->st.create() != hipSuccess || p->cs.create() != hipSuccess)
     rc = fail(P2V_E_DEVICE, "stream creation on device " + std::to_string(device));
-  if (rc == P2V_OK) rc = p2v_verifier_create(c, device, cap, &p->v);
+  p2v_verifier* v = nullptr;
+  if (rc == P2V_OK) rc = p2v_verifier_create(c, device, cap, &v);
+  p->v.reset(v);
   if (rc != P2V_OK) { pipe_free(p); return rc; }
   p->busy = true;
   std::lock_guard<std::mutex> lk(c->pool_mu);
@@ -962,28 +977,41 @@ static void pipe_release(const p2v_circuit* c, HostPipe* p, bool broken) {
   pipe_free(drop);
 }
 
+// what a chunked call of n proofs of W words needs on pipe p: the ring (made once), the device
+// statuses and their pinned copy, and for the binary path (want_ok) the same for the ok flags
+static int pipe_prepare(HostPipe* p, size_t n, size_t W, bool want_ok) {
+  if (!p->have_ring) {
+    for (int k = 0; k < HostPipe::kRing; k++) {
+      HCK(p->ring[k].alloc(p->cap * W * 8));
+      if (!p->copied[k]) HCK(p->copied[k].create());
+      if (!p->freed[k]) HCK(p->freed[k].create());
+    }
+    p->have_ring = true;
+  }
+  HCK(p->dres.grow(n));
+  if (want_ok) HCK(p->dok.grow(n));
+  HCK(p->h_res.grow(n));
+  if (want_ok) HCK(p->h_ok.grow(n));
+  return P2V_OK;
+}
+
+// the verifier capacity for m proofs in chunks of ch: one chunk in 64-proof granules (powers of
+// two), else the chunk
+static size_t pipe_cap(size_t m, size_t ch) {
+  size_t cap = 64;
+  while (cap < std::min(m, ch)) cap <<= 1;
+  if (m > ch) cap = ch;
+  return cap;
+}
+
 // verify m proofs (proof-major rows in host memory) on pipe p: one run for a single chunk (the
 // latency path: H2D, kernels, D2H on the pipe's stream); otherwise chunks of <= p->cap proofs
 // through the ring, copies on the copy stream, verification on the compute stream, statuses
 // accumulated on the device and copied back once.
 static int pipe_run(HostPipe* p, const uint64_t* src, size_t m, int8_t* results, size_t W, size_t chunk) {
   HCK(hipSetDevice(p->device));
-  if (m <= chunk) return p2v_verifier_run(p->v, src, m, results, nullptr, p->st, 0);
-  if (!p->have_ring) {
-    for (int k = 0; k < HostPipe::kRing; k++) {
-      HCK(p->ring[k].alloc(p->cap * W * 8));
-      HCK(hipEventCreateWithFlags(&p->copied[k], hipEventDisableTiming));
-      HCK(hipEventCreateWithFlags(&p->freed[k], hipEventDisableTiming));
-    }
-    p->have_ring = true;
-  }
-  if (p->dres.bytes < m) { p->dres.free_(); HCK(p->dres.alloc(m)); }
-  if (p->h_res_cap < m) {
-    if (p->h_res) (void)hipHostFree(p->h_res);
-    p->h_res = nullptr; p->h_res_cap = 0;
-    HCK(hipHostMalloc((void**)&p->h_res, m));
-    p->h_res_cap = m;
-  }
+  if (m <= chunk) return p2v_verifier_run(p->v.get(), src, m, results, nullptr, p->st, 0);
+  RCK(pipe_prepare(p, m, W, false));
   const size_t nch = (m + chunk - 1) / chunk;
   for (size_t i = 0; i < nch; i++) {
     const int b = (int)(i % HostPipe::kRing);
@@ -992,14 +1020,13 @@ static int pipe_run(HostPipe* p, const uint64_t* src, size_t m, int8_t* results,
     HCK(hipMemcpyAsync(p->ring[b].p, src + off * W, len * W * 8, hipMemcpyHostToDevice, p->cs));
     HCK(hipEventRecord(p->copied[b], p->cs));
     HCK(hipStreamWaitEvent(p->st, p->copied[b], 0));
-    const int rc = p2v_verifier_run(p->v, (const uint64_t*)p->ring[b].p, len, (int8_t*)p->dres.p + off, nullptr, p->st,
-                                    P2V_FLAG_INPUT_DEVICE | P2V_FLAG_RESULT_DEVICE | P2V_FLAG_NO_SYNC);
-    if (rc != P2V_OK) return rc;
+    RCK(p2v_verifier_run(p->v.get(), (const uint64_t*)p->ring[b].p, len, (int8_t*)p->dres.p + off, nullptr, p->st,
+                         P2V_FLAG_INPUT_DEVICE | P2V_FLAG_RESULT_DEVICE | P2V_FLAG_NO_SYNC));
     HCK(hipEventRecord(p->freed[b], p->st));
   }
-  HCK(hipMemcpyAsync(p->h_res, p->dres.p, m, hipMemcpyDeviceToHost, p->st));
+  HCK(hipMemcpyAsync(p->h_res.p, p->dres.p, m, hipMemcpyDeviceToHost, p->st));
   HCK(hipStreamSynchronize(p->st));
-  memcpy(results, p->h_res, m);
+  memcpy(results, p->h_res.p, m);
   return P2V_OK;
 }
 
@@ -1028,13 +1055,9 @@ int p2v_verify_batch_devices(const p2v_circuit* c, const uint64_t* proofs, size_
     const size_t base = n / shards, extra = n % shards;   // p2v.shard_bounds
     const size_t a = s * base + std::min<size_t>(s, extra), b = a + base + ((size_t)s < extra ? 1 : 0);
     const size_t m = b - a;
-    // one chunk: a verifier sized to the shard (64-proof granules, powers of two), else chunks
     const size_t ch = m <= 64 ? m : auto_chunk(m, chunk);
-    size_t cap = 64;
-    while (cap < std::min(m, ch)) cap <<= 1;
-    if (m > ch) cap = ch;
     HostPipe* p = nullptr;
-    int rc = pipe_acquire(c, devices[s], cap, &p);
+    int rc = pipe_acquire(c, devices[s], pipe_cap(m, ch), &p);
     if (rc == P2V_OK) {
       rc = pipe_run(p, proofs + a * W, m, results + a, W, ch);
       pipe_release(c, p, rc != P2V_OK);
@@ -1054,8 +1077,61 @@ int p2v_verify_batch_devices(const p2v_circuit* c, const uint64_t* proofs, size_
   return P2V_OK;
 }
 
-// JSON texts -> packed rows of v->in (device packer against the template, host reader for
-// the rest); codes[i] as p2v_pack_proof_json
+// ---- ingest: JSON texts or plonky2 binary proofs -> packed rows of v->in ----
+
+// A batch's texts or bytes and its offsets (rebased to the batch's first byte) on the device, in
+// j_blob / j_offs, with room for the packer's ok flags in j_ok.  rel is the offsets' host copy:
+// the caller keeps it until the stream is synchronised.
+static int stage_batch(p2v_verifier* v, const void* blob, const uint64_t* offsets, size_t n, std::vector<uint64_t>& rel, hipStream_t st) {
+  const uint64_t base = offsets[0], bytes = offsets[n] - base;
+  HCK(v->j_blob.grow(bytes + 64));   // + vector / unaligned-load slack
+  HCK(v->j_offs.grow((n + 1) * 8));
+  HCK(v->j_ok.grow(n));
+  rel.resize(n + 1);
+  for (size_t i = 0; i <= n; i++) rel[i] = offsets[i] - base;
+  HCK(hipMemcpyAsync(v->j_blob.p, (const uint8_t*)blob + base, bytes, hipMemcpyHostToDevice, st));
+  HCK(hipMemcpyAsync(v->j_offs.p, rel.data(), (n + 1) * 8, hipMemcpyHostToDevice, st));
+  return P2V_OK;
+}
+
+// the device packer's ok flags of the staged batch, read back through the pinned buffer
+static int read_ok_flags(p2v_verifier* v, size_t n, std::vector<int8_t>& okf, hipStream_t st) {
+  HCK(hipGetLastError());
+  HCK(hipMemcpyAsync(v->h_res.p, v->j_ok.p, n, hipMemcpyDeviceToHost, st));
+  HCK(hipStreamSynchronize(st));
+  okf.assign(v->h_res.p, v->h_res.p + n);
+  return P2V_OK;
+}
+
+// The proofs the device packer did not take (other formatting, exotic numbers, errors): the host
+// reader, one row at a time.  pack_row(i, row) packs proof i or throws as p2v_pack_proof_json /
+// _bytes do; codes[i] is that call's code.  n_device receives the count of device-packed proofs.
+static int host_fallback(p2v_verifier* v, size_t n, const std::vector<int8_t>& okf, int32_t* codes, size_t* n_device,
+                         hipStream_t st, const std::function<void(size_t, uint64_t*)>& pack_row) {
+  const size_t W = (size_t)v->circ->c.L.words;
+  std::vector<uint64_t> row(W);
+  if (n_device) for (size_t i = 0; i < n; i++) *n_device += okf[i] ? 1 : 0;
+  for (size_t i = 0; i < n; i++) {
+    codes[i] = P2V_OK;
+    if (okf[i]) continue;
+    try {
+      pack_row(i, row.data());
+      HCK(hipMemcpyAsync((uint64_t*)v->in.p + i * W, row.data(), W * 8, hipMemcpyHostToDevice, st));
+      HCK(hipStreamSynchronize(st));   // row is reused
+    } catch (const ShapeError&) { codes[i] = P2V_E_SHAPE; }
+    catch (...) { codes[i] = P2V_E_PARSE; }
+  }
+  return P2V_OK;
+}
+
+// h on the device in b, grown to bytes + slack
+static hipError_t put(DevBuf& b, const void* h, size_t bytes, size_t slack) {
+  hipError_t e = b.grow(bytes + slack);
+  if (e == hipSuccess && bytes) e = hipMemcpy(b.p, h, bytes, hipMemcpyHostToDevice);
+  return e;
+}
+
+// JSON texts: the device packer against the template, the host reader for the rest
 static int pack_json_into(p2v_verifier* v, const char* blob, const uint64_t* offsets, size_t n,
                           int32_t* codes, size_t* n_device, void* stream_) {
   if (n_device) *n_device = 0;
@@ -1083,12 +1159,8 @@ static int pack_json_into(p2v_verifier* v, const char* blob, const uint64_t* off
   std::vector<uint8_t> skel; std::vector<int32_t> tok;
   const bool dev_ok = v->have_tmpl && (!fresh || v->tmpl.device_form(skel, tok));
   if (fresh && dev_ok) {
-    auto put = [&](DevBuf& b, const void* h, size_t bytes) -> hipError_t {
-      if (b.bytes < bytes + 64) { b.free_(); hipError_t e = b.alloc(bytes + 64); if (e != hipSuccess) return e; }   // + vector-load slack
-      return hipMemcpy(b.p, h, bytes, hipMemcpyHostToDevice);
-    };
-    HCK(put(v->j_skel, skel.data(), skel.size()));
-    HCK(put(v->j_tok, tok.data(), tok.size() * sizeof(int32_t)));
+    HCK(put(v->j_skel, skel.data(), skel.size(), 64));   // + vector-load slack
+    HCK(put(v->j_tok, tok.data(), tok.size() * sizeof(int32_t), 64));
     v->skel_len = (int64_t)skel.size(); v->ntok = (int64_t)tok.size();
   } else if (fresh || !v->have_tmpl) {
     // a new template without a device form (or none at all): drop the previous template's
@@ -1096,59 +1168,44 @@ static int pack_json_into(p2v_verifier* v, const char* blob, const uint64_t* off
     v->skel_len = 0; v->ntok = 0;
   }
   std::vector<int8_t> okf(n, 0);
+  std::vector<uint64_t> rel;
   if (dev_ok && v->ntok > 0) {
-    const uint64_t base = offsets[0], bytes = offsets[n] - base;
-    if (v->j_blob.bytes < bytes + 64) { v->j_blob.free_(); HCK(v->j_blob.alloc(bytes + 64)); }   // + vector-load slack
-    if (v->j_offs.bytes < (n + 1) * 8) { v->j_offs.free_(); HCK(v->j_offs.alloc((n + 1) * 8)); }
-    if (v->j_ok.bytes < n) { v->j_ok.free_(); HCK(v->j_ok.alloc(n)); }
-    std::vector<uint64_t> rel(n + 1);
-    for (size_t i = 0; i <= n; i++) rel[i] = offsets[i] - base;
-    HCK(hipMemcpyAsync(v->j_blob.p, blob + base, bytes, hipMemcpyHostToDevice, st));
-    HCK(hipMemcpyAsync(v->j_offs.p, rel.data(), (n + 1) * 8, hipMemcpyHostToDevice, st));
+    RCK(stage_batch(v, blob, offsets, n, rel, st));
     k_json_pack<<<(unsigned)n, 256, 0, st>>>((const uint8_t*)v->j_blob.p, (const uint64_t*)v->j_offs.p, (int)n, (const uint8_t*)v->j_skel.p,
                                              v->skel_len, (const int32_t*)v->j_tok.p, v->ntok, (uint64_t*)v->in.p, W, (int8_t*)v->j_ok.p);
-    HCK(hipGetLastError());
-    HCK(hipMemcpyAsync(v->h_res, v->j_ok.p, n, hipMemcpyDeviceToHost, st));
-    HCK(hipStreamSynchronize(st));
-    memcpy(okf.data(), v->h_res, n);
+    RCK(read_ok_flags(v, n, okf, st));
   }
-  if (n_device) for (size_t i = 0; i < n; i++) *n_device += okf[i] ? 1 : 0;
-  // the rest (other formatting, exotic numbers, errors): the host reader, as p2v_pack_proof_json
-  for (size_t i = 0; i < n; i++) {
-    codes[i] = P2V_OK;
-    if (okf[i]) continue;
-    try {
-      JVal pj = parse_json(text(i), tlen(i));
-      pack_proof(C, pj, row.data());
-      HCK(hipMemcpyAsync((uint64_t*)v->in.p + i * W, row.data(), (size_t)W * 8, hipMemcpyHostToDevice, st));
-      HCK(hipStreamSynchronize(st));   // row is reused
-    } catch (const ShapeError&) { codes[i] = P2V_E_SHAPE; }
-    catch (...) { codes[i] = P2V_E_PARSE; }
-  }
-  return P2V_OK;
+  return host_fallback(v, n, okf, codes, n_device, st, [&](size_t i, uint64_t* dst) {
+    JVal pj = parse_json(text(i), tlen(i));
+    pack_proof(C, pj, dst);
+  });
 }
 
 // the circuit's byte map (circuit.cpp bytes_map) on the verifier's device, made once
 static int ensure_bytes_map(p2v_verifier* v) {
   if (v->have_bmap) return P2V_OK;
   const BytesMap m = bytes_map(v->circ->c);
-  auto put = [&](DevBuf& b, const void* h, size_t bytes) -> hipError_t {
-    hipError_t e = b.alloc(bytes + 16);
-    if (e == hipSuccess && bytes) e = hipMemcpy(b.p, h, bytes, hipMemcpyHostToDevice);
-    return e;
-  };
-  HCK(put(v->b_rsrc, m.run_src.data(), m.run_src.size() * 8));
-  HCK(put(v->b_rdst, m.run_dst.data(), m.run_dst.size() * 8));
-  HCK(put(v->b_rlen, m.run_len.data(), m.run_len.size() * 8));
-  HCK(put(v->b_coff, m.chk_off.data(), m.chk_off.size() * 8));
-  HCK(put(v->b_cval, m.chk_val.data(), m.chk_val.size()));
+  HCK(put(v->b_rsrc, m.run_src.data(), m.run_src.size() * 8, 16));   // (a retry after a failure reuses what is there)
+  HCK(put(v->b_rdst, m.run_dst.data(), m.run_dst.size() * 8, 16));
+  HCK(put(v->b_rlen, m.run_len.data(), m.run_len.size() * 8, 16));
+  HCK(put(v->b_coff, m.chk_off.data(), m.chk_off.size() * 8, 16));
+  HCK(put(v->b_cval, m.chk_val.data(), m.chk_val.size(), 16));
   v->nruns = (int)m.run_len.size(); v->nchk = (int)m.chk_off.size(); v->bfixed = m.fixed;
   v->have_bmap = true;
   return P2V_OK;
 }
 
-// plonky2 binary proofs -> packed rows of v->in (k_bytes_pack against the circuit's byte map,
-// the host reader for any proof that fails a check); codes[i] as p2v_pack_proof_bytes
+// k_bytes_pack against v's byte map: n proofs of src (offsets offs) into rows, ok flags into ok
+static void launch_bytes_pack(const p2v_verifier* v, const DevBuf& src, const DevBuf& offs, size_t n, void* rows, int8_t* ok, hipStream_t st) {
+  const Circuit& C = v->circ->c;
+  k_bytes_pack<<<(unsigned)n, 256, 0, st>>>((const uint8_t*)src.p, (const uint64_t*)offs.p, (int)n, (const int64_t*)v->b_rsrc.p,
+                                            (const int64_t*)v->b_rdst.p, (const int64_t*)v->b_rlen.p, v->nruns, (const int64_t*)v->b_coff.p,
+                                            (const uint8_t*)v->b_cval.p, v->nchk, v->bfixed, (int64_t)C.num_pis, C.L.pis,
+                                            (uint64_t*)rows, C.L.words, ok);
+}
+
+// plonky2 binary proofs: k_bytes_pack against the circuit's byte map, the host reader for any
+// proof that fails a check
 static int pack_bytes_into(p2v_verifier* v, const uint8_t* blob, const uint64_t* offsets, size_t n,
                            int32_t* codes, size_t* n_device, void* stream_) {
   if (n_device) *n_device = 0;
@@ -1158,37 +1215,15 @@ static int pack_bytes_into(p2v_verifier* v, const uint8_t* blob, const uint64_t*
   HCK(hipSetDevice(v->device));
   HCK(input_buf(v));
   hipStream_t st = (hipStream_t)stream_;
-  const Circuit& C = v->circ->c;
-  const int64_t W = C.L.words;
-  { const int rc = ensure_bytes_map(v); if (rc != P2V_OK) return rc; }
-  const uint64_t base = offsets[0], bytes = offsets[n] - base;
-  if (v->j_blob.bytes < bytes + 64) { v->j_blob.free_(); HCK(v->j_blob.alloc(bytes + 64)); }   // + unaligned-load slack
-  if (v->j_offs.bytes < (n + 1) * 8) { v->j_offs.free_(); HCK(v->j_offs.alloc((n + 1) * 8)); }
-  if (v->j_ok.bytes < n) { v->j_ok.free_(); HCK(v->j_ok.alloc(n)); }
-  std::vector<uint64_t> rel(n + 1);
-  for (size_t i = 0; i <= n; i++) rel[i] = offsets[i] - base;
-  HCK(hipMemcpyAsync(v->j_blob.p, blob + base, bytes, hipMemcpyHostToDevice, st));
-  HCK(hipMemcpyAsync(v->j_offs.p, rel.data(), (n + 1) * 8, hipMemcpyHostToDevice, st));
-  k_bytes_pack<<<(unsigned)n, 256, 0, st>>>((const uint8_t*)v->j_blob.p, (const uint64_t*)v->j_offs.p, (int)n, (const int64_t*)v->b_rsrc.p,
-                                            (const int64_t*)v->b_rdst.p, (const int64_t*)v->b_rlen.p, v->nruns, (const int64_t*)v->b_coff.p,
-                                            (const uint8_t*)v->b_cval.p, v->nchk, v->bfixed, (int64_t)C.num_pis, C.L.pis,
-                                            (uint64_t*)v->in.p, W, (int8_t*)v->j_ok.p);
-  HCK(hipGetLastError());
-  HCK(hipMemcpyAsync(v->h_res, v->j_ok.p, n, hipMemcpyDeviceToHost, st));
-  HCK(hipStreamSynchronize(st));
-  std::vector<int8_t> okf(v->h_res, v->h_res + n);
-  std::vector<uint64_t> row((size_t)W);
-  for (size_t i = 0; i < n; i++) {
-    codes[i] = P2V_OK;
-    if (okf[i]) { if (n_device) (*n_device)++; continue; }
-    try {
-      pack_proof_bytes(C, blob + offsets[i], (size_t)(offsets[i + 1] - offsets[i]), row.data());
-      HCK(hipMemcpyAsync((uint64_t*)v->in.p + i * W, row.data(), (size_t)W * 8, hipMemcpyHostToDevice, st));
-      HCK(hipStreamSynchronize(st));   // row is reused
-    } catch (const ShapeError&) { codes[i] = P2V_E_SHAPE; }
-    catch (...) { codes[i] = P2V_E_PARSE; }
-  }
-  return P2V_OK;
+  RCK(ensure_bytes_map(v));
+  std::vector<int8_t> okf;
+  std::vector<uint64_t> rel;
+  RCK(stage_batch(v, blob, offsets, n, rel, st));
+  launch_bytes_pack(v, v->j_blob, v->j_offs, n, v->in.p, (int8_t*)v->j_ok.p, st);
+  RCK(read_ok_flags(v, n, okf, st));
+  return host_fallback(v, n, okf, codes, n_device, st, [&](size_t i, uint64_t* dst) {
+    pack_proof_bytes(v->circ->c, blob + offsets[i], (size_t)(offsets[i + 1] - offsets[i]), dst);
+  });
 }
 
 // plonky2 binary proofs in host memory, verified through the circuit's pooled pipe: per chunk the
@@ -1207,38 +1242,14 @@ int p2v_verify_batch_bytes(const p2v_circuit* c, const uint8_t* blob, const uint
   const Circuit& C = c->c;
   const size_t W = (size_t)C.L.words;
   const size_t ch = auto_chunk(n, chunk);
-  size_t cap = 64;
-  while (cap < std::min(n, ch)) cap <<= 1;
-  if (n > ch) cap = ch;
   HostPipe* p = nullptr;
-  int rc = pipe_acquire(c, device, cap, &p);
+  int rc = pipe_acquire(c, device, pipe_cap(n, ch), &p);
   if (rc != P2V_OK) return rc;
   auto body = [&]() -> int {
     HCK(hipSetDevice(device));
-    { const int r = ensure_bytes_map(p->v); if (r != P2V_OK) return r; }
-    if (!p->have_ring) {
-      for (int k = 0; k < HostPipe::kRing; k++) {
-        HCK(p->ring[k].alloc(p->cap * W * 8));
-        HCK(hipEventCreateWithFlags(&p->copied[k], hipEventDisableTiming));
-        HCK(hipEventCreateWithFlags(&p->freed[k], hipEventDisableTiming));
-      }
-      p->have_ring = true;
-    }
-    if (p->dres.bytes < n) { p->dres.free_(); HCK(p->dres.alloc(n)); }
-    if (p->dok.bytes < n) { p->dok.free_(); HCK(p->dok.alloc(n)); }
-    if (p->h_res_cap < n) {
-      if (p->h_res) (void)hipHostFree(p->h_res);
-      p->h_res = nullptr; p->h_res_cap = 0;
-      HCK(hipHostMalloc((void**)&p->h_res, n));
-      p->h_res_cap = n;
-    }
-    if (p->h_ok_cap < n) {
-      if (p->h_ok) (void)hipHostFree(p->h_ok);
-      p->h_ok = nullptr; p->h_ok_cap = 0;
-      HCK(hipHostMalloc((void**)&p->h_ok, n));
-      p->h_ok_cap = n;
-    }
-    p2v_verifier* v = p->v;
+    p2v_verifier* v = p->v.get();
+    RCK(ensure_bytes_map(v));
+    RCK(pipe_prepare(p, n, W, true));
     const size_t nch = (n + ch - 1) / ch;
     for (size_t i = 0; i < nch; i++) {
       const int b = (int)(i % HostPipe::kRing);
@@ -1248,8 +1259,8 @@ int p2v_verify_batch_bytes(const p2v_circuit* c, const uint8_t* blob, const uint
         HCK(hipEventSynchronize(p->copied[b]));              // the slot's host offsets are no longer read
         HCK(hipStreamWaitEvent(p->cs, p->freed[b], 0));      // its device buffers' last reader is done
       }
-      if (p->bbytes[b].bytes < bytes + 64) { p->bbytes[b].free_(); HCK(p->bbytes[b].alloc(bytes + 64)); }   // + unaligned-load slack
-      if (p->boffs[b].bytes < (len + 1) * 8) { p->boffs[b].free_(); HCK(p->boffs[b].alloc((p->cap + 1) * 8)); }
+      HCK(p->bbytes[b].grow(bytes + 64));   // + unaligned-load slack
+      HCK(p->boffs[b].grow((p->cap + 1) * 8));   // for the largest chunk (len <= cap): made once
       auto& ho = p->hoffs[b];
       ho.resize(len + 1);
       for (size_t k = 0; k <= len; k++) ho[k] = offsets[off + k] - base;
@@ -1257,27 +1268,22 @@ int p2v_verify_batch_bytes(const p2v_circuit* c, const uint8_t* blob, const uint
       HCK(hipMemcpyAsync(p->boffs[b].p, ho.data(), (len + 1) * 8, hipMemcpyHostToDevice, p->cs));
       HCK(hipEventRecord(p->copied[b], p->cs));
       HCK(hipStreamWaitEvent(p->st, p->copied[b], 0));
-      k_bytes_pack<<<(unsigned)len, 256, 0, p->st>>>((const uint8_t*)p->bbytes[b].p, (const uint64_t*)p->boffs[b].p, (int)len,
-                                                      (const int64_t*)v->b_rsrc.p, (const int64_t*)v->b_rdst.p, (const int64_t*)v->b_rlen.p,
-                                                      v->nruns, (const int64_t*)v->b_coff.p, (const uint8_t*)v->b_cval.p, v->nchk, v->bfixed,
-                                                      (int64_t)C.num_pis, C.L.pis, (uint64_t*)p->ring[b].p, (int64_t)W,
-                                                      (int8_t*)p->dok.p + off);
+      launch_bytes_pack(v, p->bbytes[b], p->boffs[b], len, p->ring[b].p, (int8_t*)p->dok.p + off, p->st);
       HCK(hipGetLastError());
-      const int r = p2v_verifier_run(v, (const uint64_t*)p->ring[b].p, len, (int8_t*)p->dres.p + off, nullptr, p->st,
-                                     P2V_FLAG_INPUT_DEVICE | P2V_FLAG_RESULT_DEVICE | P2V_FLAG_NO_SYNC);
-      if (r != P2V_OK) return r;
+      RCK(p2v_verifier_run(v, (const uint64_t*)p->ring[b].p, len, (int8_t*)p->dres.p + off, nullptr, p->st,
+                           P2V_FLAG_INPUT_DEVICE | P2V_FLAG_RESULT_DEVICE | P2V_FLAG_NO_SYNC));
       HCK(hipEventRecord(p->freed[b], p->st));
     }
-    HCK(hipMemcpyAsync(p->h_res, p->dres.p, n, hipMemcpyDeviceToHost, p->st));
-    HCK(hipMemcpyAsync(p->h_ok, p->dok.p, n, hipMemcpyDeviceToHost, p->st));
+    HCK(hipMemcpyAsync(p->h_res.p, p->dres.p, n, hipMemcpyDeviceToHost, p->st));
+    HCK(hipMemcpyAsync(p->h_ok.p, p->dok.p, n, hipMemcpyDeviceToHost, p->st));
     HCK(hipStreamSynchronize(p->st));
-    memcpy(results, p->h_res, n);
+    memcpy(results, p->h_res.p, n);
     // the proofs the device packer did not take: the host reader, then one more run for those it packs
     std::vector<size_t> redo;
     std::vector<uint64_t> rows;
     for (size_t i = 0; i < n; i++) {
       codes[i] = P2V_OK;
-      if (p->h_ok[i]) { if (n_device) (*n_device)++; continue; }
+      if (p->h_ok.p[i]) { if (n_device) (*n_device)++; continue; }
       rows.resize((redo.size() + 1) * W);
       try {
         pack_proof_bytes(C, blob + offsets[i], (size_t)(offsets[i + 1] - offsets[i]), rows.data() + redo.size() * W);
@@ -1287,8 +1293,7 @@ int p2v_verify_batch_bytes(const p2v_circuit* c, const uint8_t* blob, const uint
     }
     if (!redo.empty()) {
       std::vector<int8_t> rr(redo.size());
-      const int r = pipe_run(p, rows.data(), redo.size(), rr.data(), W, p->cap);
-      if (r != P2V_OK) return r;
+      RCK(pipe_run(p, rows.data(), redo.size(), rr.data(), W, p->cap));
       for (size_t k = 0; k < redo.size(); k++) results[redo[k]] = rr[k];
     }
     return P2V_OK;
@@ -1298,9 +1303,8 @@ int p2v_verify_batch_bytes(const p2v_circuit* c, const uint8_t* blob, const uint
   return rc;
 }
 
-int p2v_verifier_pack_bytes(p2v_verifier* v, const uint8_t* blob, const uint64_t* offsets, size_t n,
-                            int32_t* codes, size_t* n_device, uint64_t* words, void* stream_) {
-  int rc = pack_bytes_into(v, blob, offsets, n, codes, n_device, stream_);
+// the packed rows of v->in back to the host (words, if wanted), zeroed where a proof did not pack
+static int finish_pack(p2v_verifier* v, int rc, size_t n, const int32_t* codes, uint64_t* words, void* stream_) {
   if (rc != P2V_OK || n == 0 || !words) return rc;
   hipStream_t st = (hipStream_t)stream_;
   const size_t W = (size_t)v->circ->c.L.words;
@@ -1309,43 +1313,37 @@ int p2v_verifier_pack_bytes(p2v_verifier* v, const uint8_t* blob, const uint64_t
   for (size_t i = 0; i < n; i++)
     if (codes[i] != P2V_OK) memset(words + i * W, 0, W * 8);
   return P2V_OK;
+}
+
+// the packed rows of v->in verified; a proof that did not pack gets its reader's status
+static int run_packed(p2v_verifier* v, int rc, size_t n, int8_t* results, const int32_t* codes, void* stream_) {
+  if (rc != P2V_OK || n == 0) return rc;
+  RCK(p2v_verifier_run(v, (const uint64_t*)v->in.p, n, results, nullptr, stream_, P2V_FLAG_INPUT_DEVICE));
+  for (size_t i = 0; i < n; i++)
+    if (codes[i] != P2V_OK) results[i] = codes[i] == P2V_E_SHAPE ? P2V_ERR_SHAPE : P2V_ERR_PARSE;
+  return P2V_OK;
+}
+
+int p2v_verifier_pack_bytes(p2v_verifier* v, const uint8_t* blob, const uint64_t* offsets, size_t n,
+                            int32_t* codes, size_t* n_device, uint64_t* words, void* stream_) {
+  return finish_pack(v, pack_bytes_into(v, blob, offsets, n, codes, n_device, stream_), n, codes, words, stream_);
 }
 
 int p2v_verifier_run_bytes(p2v_verifier* v, const uint8_t* blob, const uint64_t* offsets, size_t n,
                            int8_t* results, int32_t* codes, size_t* n_device, void* stream_) {
   if (n && !results) return fail(P2V_E_ARG, "null argument");
-  int rc = pack_bytes_into(v, blob, offsets, n, codes, n_device, stream_);
-  if (rc != P2V_OK || n == 0) return rc;
-  rc = p2v_verifier_run(v, (const uint64_t*)v->in.p, n, results, nullptr, stream_, P2V_FLAG_INPUT_DEVICE);
-  if (rc != P2V_OK) return rc;
-  for (size_t i = 0; i < n; i++)
-    if (codes[i] != P2V_OK) results[i] = codes[i] == P2V_E_SHAPE ? P2V_ERR_SHAPE : P2V_ERR_PARSE;
-  return P2V_OK;
+  return run_packed(v, pack_bytes_into(v, blob, offsets, n, codes, n_device, stream_), n, results, codes, stream_);
 }
 
 int p2v_verifier_pack_json(p2v_verifier* v, const char* blob, const uint64_t* offsets, size_t n,
                            int32_t* codes, size_t* n_device, uint64_t* words, void* stream_) {
-  int rc = pack_json_into(v, blob, offsets, n, codes, n_device, stream_);
-  if (rc != P2V_OK || n == 0 || !words) return rc;
-  hipStream_t st = (hipStream_t)stream_;
-  const size_t W = (size_t)v->circ->c.L.words;
-  HCK(hipMemcpyAsync(words, v->in.p, n * W * 8, hipMemcpyDeviceToHost, st));
-  HCK(hipStreamSynchronize(st));
-  for (size_t i = 0; i < n; i++)
-    if (codes[i] != P2V_OK) memset(words + i * W, 0, W * 8);
-  return P2V_OK;
+  return finish_pack(v, pack_json_into(v, blob, offsets, n, codes, n_device, stream_), n, codes, words, stream_);
 }
 
 int p2v_verifier_run_json(p2v_verifier* v, const char* blob, const uint64_t* offsets, size_t n,
                           int8_t* results, int32_t* codes, size_t* n_device, void* stream_) {
   if (n && !results) return fail(P2V_E_ARG, "null argument");
-  int rc = pack_json_into(v, blob, offsets, n, codes, n_device, stream_);
-  if (rc != P2V_OK || n == 0) return rc;
-  rc = p2v_verifier_run(v, (const uint64_t*)v->in.p, n, results, nullptr, stream_, P2V_FLAG_INPUT_DEVICE);
-  if (rc != P2V_OK) return rc;
-  for (size_t i = 0; i < n; i++)
-    if (codes[i] != P2V_OK) results[i] = codes[i] == P2V_E_SHAPE ? P2V_ERR_SHAPE : P2V_ERR_PARSE;
-  return P2V_OK;
+  return run_packed(v, pack_json_into(v, blob, offsets, n, codes, n_device, stream_), n, results, codes, stream_);
 }
 
 int p2v_selftest(int device, int op, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n) {
@@ -1361,26 +1359,21 @@ int p2v_selftest(int device, int op, const uint64_t* a, const uint64_t* b, uint6
   const size_t w = scalar ? 1 : 12, wo = op == 6 ? 2 : w;
   const size_t bw = op == 4 ? 24 : scalar && needs_b ? n : 2;
   DevBuf da, db, dout;
-  auto cleanup = [&]() { da.free_(); db.free_(); dout.free_(); };
-  hipError_t e = da.alloc(n * w * 8);
-  if (e == hipSuccess) e = db.alloc(bw * 8);
-  if (e == hipSuccess) e = dout.alloc(n * wo * 8);
-  if (e == hipSuccess) e = hipMemcpy(da.p, a, n * w * 8, hipMemcpyHostToDevice);
-  if (e == hipSuccess && needs_b) e = hipMemcpy(db.p, b, bw * 8, hipMemcpyHostToDevice);
-  if (e == hipSuccess) {
-    if (op >= 9) {
-      const int lanes = op == 9 ? 16 : op == 10 ? 4 : 2;
-      hipLaunchKernelGGL(k_selftest_forms, dim3((unsigned)((n * lanes + 255) / 256)), dim3(256), 0, 0, op, (const uint64_t*)da.p,
-                         (uint64_t*)dout.p, (int64_t)n);
-    } else {
-      hipLaunchKernelGGL(k_selftest, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, op, (const uint64_t*)da.p,
-                         (const uint64_t*)db.p, (uint64_t*)dout.p, (int64_t)n);
-    }
-    e = hipGetLastError();
+#define SCK(x) HCK_AS("p2v_selftest", x)
+  SCK(da.alloc(n * w * 8)); SCK(db.alloc(bw * 8)); SCK(dout.alloc(n * wo * 8));
+  SCK(hipMemcpy(da.p, a, n * w * 8, hipMemcpyHostToDevice));
+  if (needs_b) SCK(hipMemcpy(db.p, b, bw * 8, hipMemcpyHostToDevice));
+  if (op >= 9) {
+    const int lanes = op == 9 ? 16 : op == 10 ? 4 : 2;
+    hipLaunchKernelGGL(k_selftest_forms, dim3((unsigned)((n * lanes + 255) / 256)), dim3(256), 0, 0, op, (const uint64_t*)da.p,
+                       (uint64_t*)dout.p, (int64_t)n);
+  } else {
+    hipLaunchKernelGGL(k_selftest, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, op, (const uint64_t*)da.p,
+                       (const uint64_t*)db.p, (uint64_t*)dout.p, (int64_t)n);
   }
-  if (e == hipSuccess) e = hipMemcpy(out, dout.p, n * wo * 8, hipMemcpyDeviceToHost);
-  cleanup();
-  if (e != hipSuccess) return fail(P2V_E_DEVICE, std::string("p2v_selftest: ") + hipGetErrorString(e));
+  SCK(hipGetLastError());
+  SCK(hipMemcpy(out, dout.p, n * wo * 8, hipMemcpyDeviceToHost));
+#undef SCK
   return P2V_OK;
 }
 

@@ -1294,3 +1294,45 @@ def test_gpu_latency_and_batch_modes_interleaved(p2v):
                 assert np.array_equal(tr[i], ref_tr[i]), (n, i)
             else:
                 ref_tr[i] = tr[i].copy()
+
+
+def test_gpu_ingest_buffers_grow_and_shrink(p2v):
+    """The grown-on-demand buffers of the ingest paths.  One workspace takes batches of 4, 40 and
+    4 proofs through run_json / pack_json and run_bytes / pack_bytes: the second batch grows the
+    blob, offset and ok-flag buffers, the third reuses them; statuses, codes and words equal host
+    packing + p2v_verifier_run each time.  Then p2v_verify_batch_bytes with chunks of 64 on 70, 700
+    and 70 proofs: one pooled pipe of capacity 64 serves all three, its status / ok-flag buffers
+    and their pinned copies grow for the second call, and a truncated and a trailing-bytes proof
+    go to the host reader; statuses and codes equal p2v_verifier_run_bytes'."""
+    from support import proof_bytes
+    gc = gen_circuit(6, 4, 0)
+    vk = p2v.VerifierCircuitData.from_json(gc.common, gc.vkey)
+    texts = [gc.proof(1, 1), gc.proof(2, 2), gc.proof(1, 3, flags=1), gc.proof(1, 4, flags=2)]
+    bins = [proof_bytes(t) for t in texts]
+    packed4 = vk.pack_many(texts)
+    bv = p2v.BatchVerifier(vk, 0, 64)
+    want4 = bv.run(packed4)
+    assert sorted(set(want4.tolist())) == [-3, 0, 1]
+    for n in (4, 40, 4):
+        sel = np.arange(n) % 4
+        want, words_h = want4[sel], packed4[sel]
+        for run, pack, src in ((bv.run_json, bv.pack_json, texts), (bv.run_bytes, bv.pack_bytes, bins)):
+            batch = [src[i] for i in sel]
+            res, codes = run(batch)
+            assert not codes.any() and np.array_equal(res, want), (n, run.__name__)
+            words, codes = pack(batch)
+            assert not codes.any() and np.array_equal(words, words_h), (n, pack.__name__)
+        assert bv.last_json_device == n and bv.last_bytes_device == n
+    bv700 = p2v.BatchVerifier(vk, 0, 700)
+    for n in (70, 700, 70):
+        batch = [bins[i % 4] for i in range(n)]
+        if n == 700:
+            batch[130] = bins[0][: len(bins[0]) // 3]
+            batch[517] = bins[1] + b"\0" * 8
+        res_ref, codes_ref = bv700.run_bytes(batch)
+        res, codes, ndev = p2v.verify_batch_bytes(vk, batch, 0, 64)
+        assert np.array_equal(codes, codes_ref) and np.array_equal(res, res_ref), n
+        assert ndev == bv700.last_bytes_device == (698 if n == 700 else 70)
+        if n == 700:
+            assert (codes[130], codes[517]) == (p2v.E_PARSE, p2v.E_SHAPE)
+            assert (res[130], res[517]) == (p2v.ERR_PARSE, p2v.ERR_SHAPE)

@@ -419,3 +419,55 @@ def test_source_hash_covers_the_library_sources(tmp_path):
     k = tmp_path / "pkg" / "csrc" / "kernels.hip"
     k.write_bytes(k.read_bytes() + b" ")
     assert srchash.source_hash(str(tmp_path / "pkg")) != h
+
+
+def test_c_abi_argument_contract():
+    """The argument checks of the C ABI, through ctypes and without a device: a null handle or
+    pointer is P2V_E_ARG with a message, before any device call (so before P2V_E_NODEVICE); an
+    empty batch is P2V_OK; the free functions and p2v_verifier_last_timings take NULL."""
+    p2v = p2v_module()
+    L = p2v.lib()
+    gc = gen_circuit(6, 4, 0)
+    vk = p2v.VerifierCircuitData.from_json(gc.common, gc.vkey)
+    c, W = vk.handle, vk.info.proof_words
+    buf = np.zeros(W + 64, np.uint64)   # a non-null stand-in for every other pointer argument
+    b = buf.ctypes.data
+    dev0 = (ctypes.c_int * 1)(0)
+    inf = p2v._Info()
+    out = ctypes.c_void_p()
+
+    def arg_error(name, rc):
+        assert rc == p2v.E_ARG, (name, rc)
+        assert L.p2v_last_error_message(), name
+
+    arg_error("run", L.p2v_verifier_run(None, b, 1, b, None, None, 0))
+    arg_error("chain", L.p2v_verifier_chain(None, None))
+    arg_error("pack_json", L.p2v_verifier_pack_json(None, b, b, 1, b, None, b, None))
+    arg_error("run_json", L.p2v_verifier_run_json(None, b, b, 1, b, b, None, None))
+    arg_error("run_json results", L.p2v_verifier_run_json(None, b, b, 1, None, b, None, None))
+    arg_error("pack_bytes", L.p2v_verifier_pack_bytes(None, b, b, 1, b, None, b, None))
+    arg_error("run_bytes", L.p2v_verifier_run_bytes(None, b, b, 1, b, b, None, None))
+    arg_error("run_bytes results", L.p2v_verifier_run_bytes(None, b, b, 1, None, b, None, None))
+    arg_error("verify_batch circuit", L.p2v_verify_batch(None, b, 1, b, 0))
+    arg_error("verify_batch proofs", L.p2v_verify_batch(c, None, 1, b, 0))
+    arg_error("verify_batch_bytes circuit", L.p2v_verify_batch_bytes(None, b, b, 1, b, b, None, 0, 0))
+    arg_error("verify_batch_bytes codes", L.p2v_verify_batch_bytes(c, b, b, 1, b, None, None, 0, 0))
+    arg_error("count_mismatches", L.p2v_count_mismatches(b, b, 1, None, None))
+    arg_error("clock_probe stamps", L.p2v_clock_probe(None, 1, None))
+    arg_error("clock_probe nblocks", L.p2v_clock_probe(b, 0, None))
+    arg_error("pack_proof_words circuit", L.p2v_pack_proof_words(None, b, 1, b))
+    arg_error("pack_proof_words words", L.p2v_pack_proof_words(c, None, 1, b))
+    arg_error("get_info circuit", L.p2v_circuit_get_info(None, ctypes.byref(inf)))
+    arg_error("get_info info", L.p2v_circuit_get_info(c, None))
+    arg_error("devices ndevices", L.p2v_verify_batch_devices(c, b, 1, b, dev0, 0, 0))
+    arg_error("selftest op", L.p2v_selftest(0, 12, b, b, b, 1))
+    # max_batch 0 is an argument error even where no device exists
+    arg_error("create", L.p2v_verifier_create(c, 0, 0, ctypes.byref(out)))
+    assert not out.value
+    # an empty batch is done before any device is looked for
+    assert L.p2v_verify_batch(c, None, 0, None, 0) == p2v.E_OK
+    assert L.p2v_verify_batch_devices(c, None, 0, None, dev0, 1, 0) == p2v.E_OK
+    assert L.p2v_verify_batch_bytes(c, None, None, 0, None, None, None, 0, 0) == p2v.E_OK
+    assert L.p2v_verifier_last_timings(None, (ctypes.c_float * 16)(), 16) == 0
+    L.p2v_verifier_free(None)
+    L.p2v_circuit_free(None)
