@@ -198,8 +198,31 @@ int  p2v_proof_shape_json(const char* proof_json, size_t len, int* num_public_in
 int  p2v_proof_shape_words(const uint64_t* words, size_t n, int* num_public_inputs, int* final_poly_len);
 int  p2v_circuit_shape_variant(const p2v_circuit* c, int num_public_inputs, int final_poly_len, p2v_circuit** out);
 
+/* ---- key tables: many verifier keys over one CommonCircuitData (host-only) -------------
+ * The reference splits a circuit into CommonCircuitData and VerifierOnlyCircuitData
+ * (Types.hs:220-240); the latter is constants_sigmas_cap and circuit_digest alone.  Recursion
+ * trees and conditionally_verify_proof put many inner circuits on one common shape, differing
+ * only in that key.  A circuit here holds a table of keys: key 0 is the one it was constructed
+ * with (every constructor above makes a one-key circuit, and every unkeyed entry point verifies
+ * against key 0), and p2v_circuit_with_keys appends more, so that one launch verifies proof i
+ * against key key_ids[i] (p2v_verifier_run_keyed, p2v_verify_batch_keyed).
+ * Key encoding: 4 * cap_len + 4 u64 words, cap_len = 2^cap_height: the cap digests in order,
+ * 4 words each, then the 4 circuit_digest words (any u64; reduced mod p as everywhere else).
+ *   p2v_vkey_from_json     a VerifierOnlyCircuitData JSON into that encoding (dst: 4 * cap_len + 4
+ *                          words); P2V_E_PARSE on bad JSON, P2V_E_CIRCUIT when the cap is not of
+ *                          the circuit's length (validateMerkleCapLength, as the constructors)
+ *   p2v_circuit_with_keys  a new circuit (free with p2v_circuit_free) whose table is base's keys
+ *                          followed by the nkeys given ones (key_words: nkeys encodings), the same
+ *                          as base otherwise, `ext` included; more than P2V_MAX_KEYS keys in
+ *                          total: P2V_E_ARG.  p2v_circuit_shape_variant keeps the whole table.
+ *   p2v_circuit_num_keys   the number of keys in the table (>= 1; < 0: P2V_E_ARG) */
+#define P2V_MAX_KEYS 65536
+int  p2v_vkey_from_json(const p2v_circuit* c, const char* vkey_json, size_t len, uint64_t* dst);
+int  p2v_circuit_with_keys(const p2v_circuit* base, const uint64_t* key_words, size_t nkeys, p2v_circuit** out);
+int  p2v_circuit_num_keys(const p2v_circuit* c);
+
 /* ---- verification (GPU) ------------------------------------------------------------ */
-#define P2V_FLAG_INPUT_DEVICE  1u  /* `proofs` is a device pointer on the verifier's device  */
+#define P2V_FLAG_INPUT_DEVICE  1u /* `proofs` is a device pointer on the verifier's device  */
 #define P2V_FLAG_RESULT_DEVICE 2u  /* `results` (and trace) are device pointers              */
 #define P2V_FLAG_NO_SYNC       4u  /* do not synchronise the stream before returning          */
 #define P2V_FLAG_INPUT_TILED  16u  /* `proofs` is in the 64-proof tiled layout below (p2v_tile_proofs) instead of
@@ -237,6 +260,21 @@ void p2v_verifier_free(p2v_verifier* v);
  * circuits are read-only and may be shared. */
 int  p2v_verifier_run(p2v_verifier* v, const uint64_t* proofs, size_t n,
                       int8_t* results, uint64_t* trace, void* stream, uint32_t flags);
+
+/* p2v_verifier_run against the circuit's key table: proof i is verified against key key_ids[i]
+ * (n entries; a device pointer exactly when P2V_FLAG_INPUT_DEVICE is set, else a host pointer,
+ * copied through a staging buffer made by p2v_verifier_create: the run allocates nothing and
+ * stays capturable).  Every flag keeps its meaning; under P2V_FLAG_LOOKAHEAD the ids are, like
+ * the proofs, complete in device memory when the call is made.  key_ids == NULL is exactly
+ * p2v_verifier_run (every proof against key 0).  A proof whose id is >= p2v_circuit_num_keys
+ * gets the status P2V_ERR_CIRCUIT (host and device ids alike; nothing is read out of bounds) and
+ * an unspecified trace row.  The key enters the transcript's first absorb and the cap comparison
+ * of the constants/sigmas tree only (DESIGN.md "Key tables"), so a keyed batch costs what an
+ * unkeyed one does.
+ * Replaces: zipWith verifyProof over per-proof VerifierCircuitData that share their
+ * CommonCircuitData (Plonk/Verifier.hs:56-65, Types.hs:220-240). */
+int  p2v_verifier_run_keyed(p2v_verifier* v, const uint64_t* proofs, const uint32_t* key_ids, size_t n,
+                            int8_t* results, uint64_t* trace, void* stream, uint32_t flags);
 
 /* Stagger two or more workspaces that run back-to-back batches on their own streams: after
  * p2v_verifier_chain(v, prev), every later run of v starts its phase 1 (transcript + leaf
@@ -290,6 +328,11 @@ int  p2v_verifier_pack_bytes(p2v_verifier* v, const uint8_t* blob, const uint64_
  * pooled verifiers.  Replaces: map (verifyProof vkey) (Plonk/Verifier.hs:56-65). */
 int  p2v_verify_batch(const p2v_circuit* c, const uint64_t* proofs, size_t n,
                       int8_t* results, int device);
+/* The same against the circuit's key table: proof i against key key_ids[i] (host memory, n
+ * entries; ids as in p2v_verifier_run_keyed), each chunk's slice of the ids copied with the
+ * chunk.  key_ids == NULL is p2v_verify_batch. */
+int  p2v_verify_batch_keyed(const p2v_circuit* c, const uint64_t* proofs, const uint32_t* key_ids, size_t n,
+                            int8_t* results, int device);
 
 /* The same for plonky2 binary proofs (the p2v_pack_proof_bytes format): blob + offsets[n + 1] in
  * host memory (pinned for the full link rate).  Per chunk the bytes are copied on the copy stream,

@@ -26,6 +26,12 @@ extern "C" __global__ void k_phase1_pair(DevCircuit, int, int);
 extern "C" __global__ void k_transcript(DevCircuit, int);
 extern "C" __global__ void k_transcript_lane(DevCircuit, int);
 extern "C" __global__ void k_transcript_pair(DevCircuit, int);
+extern "C" __global__ void k_phase1_keyed(DevCircuit, int, int);
+extern "C" __global__ void k_phase1_lane_keyed(DevCircuit, int, int);
+extern "C" __global__ void k_phase1_pair_keyed(DevCircuit, int, int);
+extern "C" __global__ void k_transcript_keyed(DevCircuit, int);
+extern "C" __global__ void k_transcript_lane_keyed(DevCircuit, int);
+extern "C" __global__ void k_transcript_pair_keyed(DevCircuit, int);
 extern "C" __global__ void k_leaf(DevCircuit);
 extern "C" __global__ void k_merkle(DevCircuit);
 extern "C" __global__ void k_merkle_row(DevCircuit);
@@ -225,6 +231,7 @@ struct p2v_verifier {
   Stream side2;                     // small batches: k_fri beside the vanishing kernels (latency mode)
   Stream ts;                        // the lookahead transcript's
   Stream side3;                     // latency mode: the coset / misc vanishing kernels beside the Poseidon parts
+  DevBuf kid;                       // staging for key ids given in host memory (p2v_verifier_run_keyed): Bmax u32
   DevBuf in, chal, chal2, leafdig, mk, fbits, qvals, van, vparts, lutre, lutpart, res, trace;
   DevBuf m_plan, m_fol, m_chain, m_count, m_fix, m_badq, m_node;   // shared-node Merkle paths (dev.h mcse)
   DevBuf t_cs, t_kis, t_gkind, t_gpar, t_ggrp, t_gwoff, t_w, t_gs, t_ge, t_lin, t_lout, t_loff, t_llen, t_tw, t_ops, t_vit, t_rin, t_rout, t_roff, t_rch, t_pbase, t_pw;
@@ -252,6 +259,7 @@ struct HostPipe {
   PinnedBuf h_res, h_ok;          // pinned staging for dres and dok
   Event copied[kRing], freed[kRing];
   DevBuf ring[kRing];
+  DevBuf kring[kRing];            // the chunks' key ids (p2v_verify_batch_keyed): cap u32 each
   DevBuf dres;                    // device statuses of the whole call (grown on demand)
   // binary-proof ingest (p2v_verify_batch_bytes): per ring slot the chunk's bytes and offsets on
   // the device, the offsets' host copy (hoffs, rewritten once the slot's previous copy is done),
@@ -375,7 +383,7 @@ std::vector<int32_t> transcript_ops(const Circuit& C, DevCircuit& d) {
   std::vector<int32_t> ops;
   auto op = [&](int t, int64_t a_, int64_t n_) { ops.push_back(t); ops.push_back((int32_t)a_); ops.push_back((int32_t)n_); };
   const int r = d.r, C4 = 4 * C.cap_len;
-  op(TOP_ABSORB_DIGEST, 0, 4);
+  op(TOP_ABSORB_DIGEST, 0, 4);   // stays op 0: the keyed transcripts take it before the op loop (kernels.hip)
   op(TOP_ABSORB_PIH, 0, 4);
   op(TOP_ABSORB_SOA, L.wcap, C4);
   op(TOP_SQUEEZE, CH_BETA(d), r);
@@ -529,6 +537,32 @@ int p2v_circuit_shape_variant(const p2v_circuit* pc, int num_public_inputs, int 
   } catch (const std::exception& e) { return fail(P2V_E_SHAPE, e.what()); }
 }
 
+int p2v_vkey_from_json(const p2v_circuit* pc, const char* vkey_json, size_t len, uint64_t* dst) {
+  if (!pc || !vkey_json || !dst) return fail(P2V_E_ARG, "null argument");
+  return guarded(P2V_E_PARSE, [&] { vkey_words(pc->c, parse_json(vkey_json, len), dst); });
+}
+
+int p2v_circuit_with_keys(const p2v_circuit* base, const uint64_t* key_words, size_t nkeys, p2v_circuit** out) {
+  if (!base || !out || (nkeys && !key_words)) return fail(P2V_E_ARG, "null argument");
+  *out = nullptr;
+  const Circuit& B = base->c;
+  if (nkeys > (size_t)P2V_MAX_KEYS || B.num_keys() + nkeys > (size_t)P2V_MAX_KEYS)
+    return fail(P2V_E_ARG, "p2v_circuit_with_keys: more than P2V_MAX_KEYS keys");
+  return guarded(P2V_E_ARG, [&] {
+    auto v = std::make_unique<p2v_circuit>();
+    v->c = B;
+    const size_t nw = nkeys * (size_t)B.key_words();
+    v->c.extra_keys.reserve(B.extra_keys.size() + nw);
+    for (size_t i = 0; i < nw; i++) v->c.extra_keys.push_back(key_words[i] % gl::P);
+    *out = v.release();
+  });
+}
+
+int p2v_circuit_num_keys(const p2v_circuit* pc) {
+  if (!pc) return fail(P2V_E_ARG, "null argument");
+  return (int)pc->c.num_keys();
+}
+
 int p2v_pack_proofs_json(const p2v_circuit* pc, const char* const* jsons, const size_t* lens, size_t n, uint64_t* dst,
                          int32_t* codes, int threads) {
   if (!pc || (n && (!jsons || !lens || !dst || !codes))) return fail(P2V_E_ARG, "null argument");
@@ -635,7 +669,17 @@ int p2v_verifier_create(const p2v_circuit* pc, int device, size_t max_batch, p2v
   const CircuitTables t = circuit_tables(C);
   d.n_lut_pieces = t.pbase.back();
 #define ACK(x) HCK_AS("device allocation", x)
-  ACK(upload(v->t_cs, C.cs_cap, d.cs_cap)); ACK(upload(v->t_kis, C.k_is, d.k_is));
+  {   // the key table [nkeys][4 cap_len + 4]; key 0 leads it, so its cap is the unkeyed runs' cs_cap
+    std::vector<uint64_t> keys(C.cs_cap);
+    keys.insert(keys.end(), C.digest, C.digest + 4);
+    keys.insert(keys.end(), C.extra_keys.begin(), C.extra_keys.end());
+    keys.insert(keys.end(), 8, 0);   // padding the keyed transcripts may read and drop (dev.h)
+    ACK(upload(v->t_cs, keys, d.keys));
+    d.cs_cap = d.keys;
+    d.nkeys = (int32_t)C.num_keys();
+  }
+  ACK(v->kid.alloc(v->Bmax * sizeof(uint32_t)));
+  ACK(upload(v->t_kis, C.k_is, d.k_is));
   ACK(upload(v->t_gkind, t.gkind, d.gate_kind)); ACK(upload(v->t_gpar, t.gpar, d.gate_par)); ACK(upload(v->t_ggrp, t.ggrp, d.gate_grp));
   ACK(upload(v->t_gwoff, t.gwoff, d.gate_woff)); ACK(upload(v->t_w, t.wts, d.weights)); ACK(upload(v->t_gs, t.gs, d.grp_start)); ACK(upload(v->t_ge, t.ge, d.grp_end));
   ACK(upload(v->t_lin, t.lin, d.lut_in)); ACK(upload(v->t_lout, t.lout, d.lut_out)); ACK(upload(v->t_loff, t.loff, d.lut_off)); ACK(upload(v->t_llen, t.llen, d.lut_len));
@@ -712,13 +756,16 @@ void p2v_tile_proofs(const uint64_t* pm, size_t n, size_t W, uint64_t* tiled) {
 }
 
 // the transcript form's kernel (tl lanes per proof; 1: lane, 2: pair, else row / quad): with the
-// leaf hashing in its launch, and on its own (the lookahead path)
+// leaf hashing in its launch, and on its own (the lookahead path).  A keyed run (d.key_id set)
+// takes the kernels whose digest absorb reads the lane's key; the unkeyed kernels are untouched.
 static void launch_phase1(const DevCircuit& d, int tl, int nt_blocks, int leaf_blocks, hipStream_t s) {
-  auto* k = tl == 1 ? k_phase1_lane : tl == 2 ? k_phase1_pair : k_phase1;
+  auto* k = d.key_id ? (tl == 1 ? k_phase1_lane_keyed : tl == 2 ? k_phase1_pair_keyed : k_phase1_keyed)
+                     : (tl == 1 ? k_phase1_lane : tl == 2 ? k_phase1_pair : k_phase1);
   k<<<nt_blocks + leaf_blocks, 256, 0, s>>>(d, nt_blocks, tl);
 }
 static void launch_transcript(const DevCircuit& d, int tl, int nt_blocks, hipStream_t s) {
-  auto* k = tl == 1 ? k_transcript_lane : tl == 2 ? k_transcript_pair : k_transcript;
+  auto* k = d.key_id ? (tl == 1 ? k_transcript_lane_keyed : tl == 2 ? k_transcript_pair_keyed : k_transcript_keyed)
+                     : (tl == 1 ? k_transcript_lane : tl == 2 ? k_transcript_pair : k_transcript);
   k<<<nt_blocks, 256, 0, s>>>(d, tl);
 }
 // one class of vanishing items, [first, last) of d.vitems: one wave per item and 64-proof tile
@@ -727,6 +774,12 @@ static void launch_vanish(void (*k)(DevCircuit), int first, int last, int NPB, h
 }
 
 int p2v_verifier_run(p2v_verifier* v, const uint64_t* proofs, size_t n, int8_t* results, uint64_t* trace, void* stream_, uint32_t flags) {
+  return p2v_verifier_run_keyed(v, proofs, nullptr, n, results, trace, stream_, flags);
+}
+
+// key_ids == nullptr: every proof against key 0, the kernels' unkeyed path (d.key_id stays null)
+int p2v_verifier_run_keyed(p2v_verifier* v, const uint64_t* proofs, const uint32_t* key_ids, size_t n, int8_t* results,
+                           uint64_t* trace, void* stream_, uint32_t flags) {
   if (!v || (!proofs && n) || !results) return fail(P2V_E_ARG, "null argument");
   if (n > v->max_batch) return fail(P2V_E_ARG, "batch larger than max_batch");
   if (n == 0) return P2V_OK;
@@ -746,6 +799,11 @@ int p2v_verifier_run(p2v_verifier* v, const uint64_t* proofs, size_t n, int8_t* 
     HCK(input_buf(v));
     HCK(hipMemcpyAsync(v->in.p, proofs, in_words * 8, hipMemcpyHostToDevice, st));
     src = (const uint64_t*)v->in.p;
+  }
+  d.key_id = key_ids;
+  if (key_ids && !(flags & P2V_FLAG_INPUT_DEVICE)) {
+    HCK(hipMemcpyAsync(v->kid.p, key_ids, n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    d.key_id = (const uint32_t*)v->kid.p;
   }
   int8_t* dres = (flags & P2V_FLAG_RESULT_DEVICE) ? results : (int8_t*)v->res.p;
   uint64_t* dtrace = nullptr;
@@ -983,6 +1041,7 @@ static int pipe_prepare(HostPipe* p, size_t n, size_t W, bool want_ok) {
   if (!p->have_ring) {
     for (int k = 0; k < HostPipe::kRing; k++) {
       HCK(p->ring[k].alloc(p->cap * W * 8));
+      HCK(p->kring[k].alloc(p->cap * sizeof(uint32_t)));
       if (!p->copied[k]) HCK(p->copied[k].create());
       if (!p->freed[k]) HCK(p->freed[k].create());
     }
@@ -1007,10 +1066,11 @@ static size_t pipe_cap(size_t m, size_t ch) {
 // verify m proofs (proof-major rows in host memory) on pipe p: one run for a single chunk (the
 // latency path: H2D, kernels, D2H on the pipe's stream); otherwise chunks of <= p->cap proofs
 // through the ring, copies on the copy stream, verification on the compute stream, statuses
-// accumulated on the device and copied back once.
-static int pipe_run(HostPipe* p, const uint64_t* src, size_t m, int8_t* results, size_t W, size_t chunk) {
+// accumulated on the device and copied back once.  key_ids (host memory, or null: key 0): proof
+// i's key, each chunk's slice copied with the chunk.
+static int pipe_run(HostPipe* p, const uint64_t* src, const uint32_t* key_ids, size_t m, int8_t* results, size_t W, size_t chunk) {
   HCK(hipSetDevice(p->device));
-  if (m <= chunk) return p2v_verifier_run(p->v.get(), src, m, results, nullptr, p->st, 0);
+  if (m <= chunk) return p2v_verifier_run_keyed(p->v.get(), src, key_ids, m, results, nullptr, p->st, 0);
   RCK(pipe_prepare(p, m, W, false));
   const size_t nch = (m + chunk - 1) / chunk;
   for (size_t i = 0; i < nch; i++) {
@@ -1018,10 +1078,11 @@ static int pipe_run(HostPipe* p, const uint64_t* src, size_t m, int8_t* results,
     const size_t off = i * chunk, len = std::min(chunk, m - off);
     if (i >= (size_t)HostPipe::kRing) HCK(hipStreamWaitEvent(p->cs, p->freed[b], 0));   // its last reader is done
     HCK(hipMemcpyAsync(p->ring[b].p, src + off * W, len * W * 8, hipMemcpyHostToDevice, p->cs));
+    if (key_ids) HCK(hipMemcpyAsync(p->kring[b].p, key_ids + off, len * sizeof(uint32_t), hipMemcpyHostToDevice, p->cs));
     HCK(hipEventRecord(p->copied[b], p->cs));
     HCK(hipStreamWaitEvent(p->st, p->copied[b], 0));
-    RCK(p2v_verifier_run(p->v.get(), (const uint64_t*)p->ring[b].p, len, (int8_t*)p->dres.p + off, nullptr, p->st,
-                         P2V_FLAG_INPUT_DEVICE | P2V_FLAG_RESULT_DEVICE | P2V_FLAG_NO_SYNC));
+    RCK(p2v_verifier_run_keyed(p->v.get(), (const uint64_t*)p->ring[b].p, key_ids ? (const uint32_t*)p->kring[b].p : nullptr, len,
+                               (int8_t*)p->dres.p + off, nullptr, p->st, P2V_FLAG_INPUT_DEVICE | P2V_FLAG_RESULT_DEVICE | P2V_FLAG_NO_SYNC));
     HCK(hipEventRecord(p->freed[b], p->st));
   }
   HCK(hipMemcpyAsync(p->h_res.p, p->dres.p, m, hipMemcpyDeviceToHost, p->st));
@@ -1039,8 +1100,10 @@ static size_t auto_chunk(size_t m, size_t chunk) {
   return std::min<size_t>(16384, std::max<size_t>(256, c));
 }
 
-int p2v_verify_batch_devices(const p2v_circuit* c, const uint64_t* proofs, size_t n, int8_t* results,
-                             const int* devices, int ndevices, size_t chunk) {
+// p2v_verify_batch_devices and p2v_verify_batch_keyed: shards over `devices`, proof i against key
+// key_ids[i] (null: key 0)
+static int verify_batch_sharded(const p2v_circuit* c, const uint64_t* proofs, const uint32_t* key_ids, size_t n, int8_t* results,
+                                const int* devices, int ndevices, size_t chunk) {
   if (!c || !devices || ndevices <= 0 || (n && (!proofs || !results))) return fail(P2V_E_ARG, "null argument / no devices");
   if (n == 0) return P2V_OK;
   int ndev = 0;
@@ -1059,7 +1122,7 @@ int p2v_verify_batch_devices(const p2v_circuit* c, const uint64_t* proofs, size_
     HostPipe* p = nullptr;
     int rc = pipe_acquire(c, devices[s], pipe_cap(m, ch), &p);
     if (rc == P2V_OK) {
-      rc = pipe_run(p, proofs + a * W, m, results + a, W, ch);
+      rc = pipe_run(p, proofs + a * W, key_ids ? key_ids + a : nullptr, m, results + a, W, ch);
       pipe_release(c, p, rc != P2V_OK);
     }
     if (rc != P2V_OK) msgs[s] = g_err;   // g_err is thread-local: carry the message back
@@ -1075,6 +1138,16 @@ int p2v_verify_batch_devices(const p2v_circuit* c, const uint64_t* proofs, size_
     if (rcs[s] != P2V_OK)
       return fail(rcs[s], "shard " + std::to_string(s) + " (device " + std::to_string(devices[s]) + "): " + msgs[s]);
   return P2V_OK;
+}
+
+int p2v_verify_batch_devices(const p2v_circuit* c, const uint64_t* proofs, size_t n, int8_t* results,
+                             const int* devices, int ndevices, size_t chunk) {
+  return verify_batch_sharded(c, proofs, nullptr, n, results, devices, ndevices, chunk);
+}
+
+int p2v_verify_batch_keyed(const p2v_circuit* c, const uint64_t* proofs, const uint32_t* key_ids, size_t n, int8_t* results, int device) {
+  if (!c || (n && (!proofs || !results))) return fail(P2V_E_ARG, "null argument");
+  return verify_batch_sharded(c, proofs, key_ids, n, results, &device, 1, 0);
 }
 
 // ---- ingest: JSON texts or plonky2 binary proofs -> packed rows of v->in ----
@@ -1293,7 +1366,7 @@ int p2v_verify_batch_bytes(const p2v_circuit* c, const uint8_t* blob, const uint
     }
     if (!redo.empty()) {
       std::vector<int8_t> rr(redo.size());
-      RCK(pipe_run(p, rows.data(), redo.size(), rr.data(), W, p->cap));
+      RCK(pipe_run(p, rows.data(), nullptr, redo.size(), rr.data(), W, p->cap));
       for (size_t k = 0; k < redo.size(); k++) results[redo[k]] = rr[k];
     }
     return P2V_OK;
@@ -1401,8 +1474,7 @@ int p2v_verifier_last_timings(const p2v_verifier* v, float* out, int max) {
 }
 
 int p2v_verify_batch(const p2v_circuit* c, const uint64_t* proofs, size_t n, int8_t* results, int device) {
-  if (!c || (n && (!proofs || !results))) return fail(P2V_E_ARG, "null argument");
-  return p2v_verify_batch_devices(c, proofs, n, results, &device, 1, 0);
+  return p2v_verify_batch_keyed(c, proofs, nullptr, n, results, device);
 }
 
 }  // extern "C"

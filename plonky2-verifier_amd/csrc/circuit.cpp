@@ -238,6 +238,16 @@ Circuit parse_circuit(const JVal& common, const JVal& vkey, uint32_t ext) {
   return C;
 }
 
+void vkey_words(const Circuit& C, const JVal& vkey, uint64_t* dst) {
+  std::vector<uint64_t> cap;
+  for (const auto& d : vkey.at("constants_sigmas_cap").arr()) { uint64_t e[4]; digest_of(d, e); cap.insert(cap.end(), e, e + 4); }
+  uint64_t dg[4];
+  digest_of(vkey.at("circuit_digest"), dg);
+  if ((int)cap.size() != 4 * C.cap_len) throw CircuitError("validateMerkleCapLength: constants_sigmas_cap has wrong size");
+  std::copy(cap.begin(), cap.end(), dst);
+  std::copy(dg, dg + 4, dst + cap.size());
+}
+
 // Validation (circuit-level `error`s) and everything derived from the decoded fields; shared by
 // the JSON and the word-encoded entry points.
 static void finalize_circuit(Circuit& C) {

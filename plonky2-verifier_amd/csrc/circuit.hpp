@@ -58,7 +58,13 @@ struct Circuit {
   // VerifierOnlyCircuitData (Types.hs:236-240)
   std::vector<uint64_t> cs_cap;             // 4 words per digest
   uint64_t digest[4] = {0, 0, 0, 0};
-  int final_len_override = -1;               // shape variant (circuit_shape_variant): final_poly length
+  // further verifier keys of the same common data (p2v_circuit_with_keys): key k >= 1 at
+  // extra_keys[(k - 1) * key_words()], in the key encoding [cap digests | circuit_digest]; key 0
+  // is cs_cap / digest above
+  std::vector<uint64_t> extra_keys;
+  int key_words() const { return 4 * cap_len + 4; }
+  size_t num_keys() const { return 1 + extra_keys.size() / (size_t)key_words(); }
+  int final_len_override = -1;              // shape variant (circuit_shape_variant): final_poly length
   // derived
   int cap_len = 0, final_len = 0;
   int oracle_width[4] = {0, 0, 0, 0};       // data columns per initial oracle (Plonk/FRI.hs:56-65)
@@ -77,6 +83,9 @@ Circuit parse_circuit(const JVal& common, const JVal& vkey, uint32_t ext = 0);  
 // the same from the word-encoded Types.hs values (include/p2v.h, "Word-encoded values")
 Circuit parse_circuit_words(const uint64_t* words, size_t n, uint32_t ext = 0);   // throws ParseError / CircuitError
 void pack_proof_words(const Circuit& c, const uint64_t* words, size_t n, uint64_t* dst);   // ParseError / ShapeError
+// a VerifierOnlyCircuitData JSON in the key encoding (c.key_words() words: the cap digests, then
+// circuit_digest); ParseError, or CircuitError when the cap is not of the circuit's length
+void vkey_words(const Circuit& c, const JVal& vkey, uint64_t* dst);
 // plonky2's binary ProofWithPublicInputs serialization (circuit.cpp); ParseError / ShapeError
 void pack_proof_bytes(const Circuit& c, const uint8_t* bytes, size_t n, uint64_t* dst);
 // The same format as a fixed map for the device packer (json_pack.hip k_bytes_pack): runs of u64

@@ -44,7 +44,15 @@ struct DevCircuit {
   uint64_t step_shift_inv[P2V_MAX_STEPS + 1];
   uint64_t inv_arity[P2V_MAX_STEPS];          // 1 / 2^arity
   // device tables
-  const uint64_t* cs_cap;          // [cap_len][4]
+  const uint64_t* cs_cap;          // [cap_len][4]: key 0's cap (the head of `keys`)
+  // the verifier keys of the circuit's table, [nkeys][4 * cap_len + 4]: cap digests, then the
+  // circuit digest (include/p2v.h "key tables"), then 8 words of padding (the keyed transcripts
+  // read a few words past a key's digest and drop them, kernels.hip).  key_id[n]: the key of
+  // each proof of this run (p2v_verifier_run_keyed), or nullptr: every proof against key 0, read
+  // from cs_cap / digest above as scalar operands (wave-uniform test; devcommon.h lane_key())
+  const uint64_t* keys;
+  const uint32_t* key_id;
+  int32_t nkeys;
   const uint64_t* k_is;            // [num_routed]
   const int32_t* gate_kind;        // [n_gates]
   const int64_t* gate_par;         // [n_gates][3]

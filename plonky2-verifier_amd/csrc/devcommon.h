@@ -24,6 +24,14 @@ __device__ __forceinline__ uint64_t ld(const DevCircuit& c, int64_t w, int p) {
   return c.soa[base + w * c.wstride];
 }
 __device__ __forceinline__ E lde(const DevCircuit& c, int64_t w, int p) { return E{ld(c, w, p), ld(c, w + 1, p)}; }
+// Lane p's verifier key in a keyed run (c.key_id != nullptr; callers test that, wave-uniform,
+// and keep the scalar c.cs_cap / c.digest operands otherwise): cap digests at [0, 4 cap_len), the
+// circuit digest after them.  Lanes past n take proof n - 1's id, as they take its row; an id past
+// the table is clamped here (no read out of bounds) and k_status reports it as P2V_ERR_CIRCUIT.
+__device__ __forceinline__ const uint64_t* lane_key(const DevCircuit& c, int p) {
+  const uint32_t id = min(c.key_id[min(p, c.n - 1)], (uint32_t)(c.nkeys - 1));
+  return c.keys + (int64_t)id * (4 * c.cap_len + 4);
+}
 __device__ __forceinline__ uint64_t& chal(const DevCircuit& c, int64_t w, int p) { return c.chal[w * c.B + p]; }
 __device__ __forceinline__ E chal_e(const DevCircuit& c, int64_t w, int p) { return E{c.chal[w * c.B + p], c.chal[(w + 1) * c.B + p]}; }
 

@@ -215,8 +215,13 @@ struct LaneForm {
   __device__ __forceinline__ E fold(E h, const E (&)[1]) const { return h; }
 };
 
-// The interpreter, written once for the four forms: ONE permutation call site per duplex rule
-template <class F>
+// The interpreter, written once for the four forms: ONE permutation call site per duplex rule.
+// KEYED (a parameter of the launch, api.cpp): the digest is the lane's key's (devcommon.h
+// lane_key()), placed into the empty sponge before the op loop -- the program's first op is always
+// the digest absorb (api.cpp transcript_ops), 4 words into rate positions 0..3 of a zero state --
+// so it holds no register beyond the state's.  The unkeyed kernels keep the digest as a scalar
+// operand of the interpreter, and their registers.
+template <bool KEYED, class F>
 __device__ __forceinline__ void transcript(const DevCircuit& c, int p, const F& f) {
   const bool leader = f.t == 0;
   constexpr int RW = F::W < 8 ? F::W : 8;   // a lane's words that can be rate positions
@@ -239,7 +244,20 @@ __device__ __forceinline__ void transcript(const DevCircuit& c, int p, const F& 
   bool absorbing = true;
   const uint64_t qmask = (1ULL << c.lde_bits) - 1;
   uint64_t fa0 = 0, fa1 = 0;   // FRI alpha, kept in registers for the reduced openings below
-  for (int o = 0; o < c.ntops; o++) {
+  if constexpr (KEYED) {
+    // one address per lane and constant offsets from it: a lane's words past position 3 read on
+    // into the table (at most 6 words past the key: the table ends in 8 words of padding, dev.h)
+    // and are dropped by the select
+    const int first = F::W * f.t < 4 ? F::W * f.t : 4;
+    const uint64_t* kd = lane_key(c, p) + 4 * c.cap_len + first;
+#pragma unroll
+    for (int j = 0; j < RW; j++) {
+      const uint64_t u = kd[j];
+      x[j] = first + j < 4 ? u : 0;
+    }
+    nbuf = 4;
+  }
+  for (int o = KEYED ? 1 : 0; o < c.ntops; o++) {
     const int type = c.tops[3 * o], a = c.tops[3 * o + 1], n = c.tops[3 * o + 2];
     if (type == TOP_COPY) {   // mkLookupDeltaList (betas ++ gammas ++ ...), Challenge/Verifier.hs:36-40,82-86
       if (leader) for (int k = 0; k < n; k++) chal(c, a + k, p) = chal(c, a - 3 * c.r + k, p);
@@ -269,7 +287,7 @@ __device__ __forceinline__ void transcript(const DevCircuit& c, int p, const F& 
             if constexpr (F::CLAMP) { const uint64_t u = ld(c, (int64_t)a + (mine[j] ? w : 0), p); v[j] = mine[j] ? u : 0; }
             else { if (mine[j]) v[j] = ld(c, (int64_t)a + w, p); }
           } else if (type == TOP_ABSORB_PIH) { const int q = w & 3; v[j] = q == 0 ? pih[0] : q == 1 ? pih[1] : q == 2 ? pih[2] : pih[3]; }
-          else v[j] = c.digest[w & 3];
+          else if constexpr (!KEYED) v[j] = c.digest[w & 3];
         }
         if (full && F::LOAD_FIRST) f.permute(x);
 #pragma unroll
@@ -312,19 +330,19 @@ union TLdsAny { qp::TLds q; pp::TLdsP p; lp::TLdsL l; };
 // one workgroup of transcripts: `tl` lanes per proof (16: row form, 4: quad form); FORM 1: the
 // lane form, FORM 2: the pair form (kernels of their own, so that their register demand does
 // not touch the others')
-template <int FORM = 0>
+template <int FORM = 0, bool KEYED = false>
 __device__ __forceinline__ void transcript_block(const DevCircuit& c, int tl, TLdsAny& U) {
   const int g = blockIdx.x * 256 + threadIdx.x;
   if constexpr (FORM == 1) {
-    if (g < c.B) transcript(c, g, LaneForm{});
+    if (g < c.B) transcript<KEYED>(c, g, LaneForm{});
   } else if constexpr (FORM == 2) {
-    if ((g >> 1) < c.B) transcript(c, g >> 1, PairForm{g & 1, U.p});
+    if ((g >> 1) < c.B) transcript<KEYED>(c, g >> 1, PairForm{g & 1, U.p});
   } else if (tl == 16) {
     lp::Row LR;
     lp::init(LR, U.l, threadIdx.x);
-    if ((g >> 4) < c.B) transcript(c, g >> 4, RowForm(LR, U.l));
+    if ((g >> 4) < c.B) transcript<KEYED>(c, g >> 4, RowForm(LR, U.l));
   } else {
-    if ((g >> 2) < c.B) transcript(c, g >> 2, QuadForm{g & 3, U.q});
+    if ((g >> 2) < c.B) transcript<KEYED>(c, g >> 2, QuadForm{g & 3, U.q});
   }
 }
 
@@ -338,7 +356,7 @@ __device__ __forceinline__ void tlds_fill_form(TLdsAny& T, int tl) {
 // blocks [0, nt_blocks): transcripts, `tl` lanes per proof (16: row form, 4: quad form) at
 // raised wave priority so co-resident leaf waves do not stretch the serial chain; the
 // rest: leaf hashing, 4 units per block.  Transcript blocks come first so they start first.
-template <int FORM>
+template <int FORM, bool KEYED = false>
 __device__ __forceinline__ void phase1_body(const DevCircuit& c, int nt_blocks, int tl) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   __shared__ TLdsAny T;
@@ -346,7 +364,7 @@ __device__ __forceinline__ void phase1_body(const DevCircuit& c, int nt_blocks, 
     __builtin_amdgcn_s_setprio(3);
     if constexpr (FORM == 0) tlds_fill_form(T, tl);
     if constexpr (FORM == 2) pp::tlds_fill(T.p, threadIdx.x, 256);
-    transcript_block<FORM>(c, tl, T);
+    transcript_block<FORM, KEYED>(c, tl, T);
     return;
   }
   const int unit = ((int)blockIdx.x - nt_blocks) * 4 + wave;
@@ -363,6 +381,16 @@ extern "C" __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_pe
 // the pair-form transcript (P2V_TRANSCRIPT=pair) with the leaf hashing
 extern "C" __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) k_phase1_pair(DevCircuit c, int nt_blocks, int tl) {
   phase1_body<2>(c, nt_blocks, tl);
+}
+// the three with per-proof verifier keys (p2v_verifier_run_keyed)
+extern "C" __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) k_phase1_keyed(DevCircuit c, int nt_blocks, int tl) {
+  phase1_body<0, true>(c, nt_blocks, tl);
+}
+extern "C" __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) k_phase1_lane_keyed(DevCircuit c, int nt_blocks, int tl) {
+  phase1_body<1, true>(c, nt_blocks, tl);
+}
+extern "C" __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) k_phase1_pair_keyed(DevCircuit c, int nt_blocks, int tl) {
+  phase1_body<2, true>(c, nt_blocks, tl);
 }
 
 // The same two halves as separate launches, for the transcript lookahead (P2V_FLAG_LOOKAHEAD,
@@ -385,6 +413,24 @@ extern "C" __global__ void __launch_bounds__(256) k_transcript_pair(DevCircuit c
   __shared__ TLdsAny T;
   pp::tlds_fill(T.p, threadIdx.x, 256);
   transcript_block<2>(c, tl, T);
+}
+// and with per-proof verifier keys
+extern "C" __global__ void __launch_bounds__(256) k_transcript_keyed(DevCircuit c, int tl) {
+  __builtin_amdgcn_s_setprio(3);
+  __shared__ TLdsAny T;
+  tlds_fill_form(T, tl);
+  transcript_block<0, true>(c, tl, T);
+}
+extern "C" __global__ void __launch_bounds__(256) k_transcript_lane_keyed(DevCircuit c, int tl) {
+  __builtin_amdgcn_s_setprio(3);
+  __shared__ TLdsAny T;
+  transcript_block<1, true>(c, tl, T);
+}
+extern "C" __global__ void __launch_bounds__(256) k_transcript_pair_keyed(DevCircuit c, int tl) {
+  __builtin_amdgcn_s_setprio(3);
+  __shared__ TLdsAny T;
+  pp::tlds_fill(T.p, threadIdx.x, 256);
+  transcript_block<2, true>(c, tl, T);
 }
 extern "C" __global__ void __launch_bounds__(256) k_leaf(DevCircuit c) {
   const int unit = (int)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -434,7 +480,7 @@ __device__ __forceinline__ bool cap_ok(const DevCircuit& c, int t, uint32_t idx,
 #pragma unroll
   for (int i = 0; i < 4; i++) {
     uint64_t root;
-    if (t == 0) root = c.cs_cap[ci * 4 + i];
+    if (t == 0) root = c.key_id ? lane_key(c, p)[ci * 4 + i] : c.cs_cap[ci * 4 + i];   // keyed run (wave-uniform): the lane's key
     else if (t == 1) root = ld(c, c.wcap + ci * 4 + i, p);
     else if (t == 2) root = ld(c, c.zcap + ci * 4 + i, p);
     else if (t == 3) root = ld(c, c.qcap + ci * 4 + i, p);
@@ -767,7 +813,7 @@ extern "C" __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_pe
     const uint32_t ci = ok ? idx : 0;
     uint64_t root = 0;
     if (L < 4) {
-      if (t == 0) root = c.cs_cap[ci * 4 + L];
+      if (t == 0) root = c.key_id ? lane_key(c, p)[ci * 4 + L] : c.cs_cap[ci * 4 + L];
       else if (t == 1) root = ld(c, c.wcap + ci * 4 + L, p);
       else if (t == 2) root = ld(c, c.zcap + ci * 4 + L, p);
       else if (t == 3) root = ld(c, c.qcap + ci * 4 + L, p);
@@ -851,7 +897,7 @@ extern "C" __global__ void __launch_bounds__(256) k_merkle_row(DevCircuit c) {
   const uint32_t ci = ok ? idx : 0;
   uint64_t root = 0;
   if (L < 4) {
-    if (t == 0) root = c.cs_cap[ci * 4 + L];
+    if (t == 0) root = c.key_id ? lane_key(c, p)[ci * 4 + L] : c.cs_cap[ci * 4 + L];
     else if (t == 1) root = ld(c, c.wcap + ci * 4 + L, p);
     else if (t == 2) root = ld(c, c.zcap + ci * 4 + L, p);
     else if (t == 3) root = ld(c, c.qcap + ci * 4 + L, p);
@@ -1110,6 +1156,9 @@ extern "C" __global__ void __launch_bounds__(256) k_status(DevCircuit c, int8_t*
       if (!((bits >> 31) & 1u)) st = 0;
     }
   }
+  // a key id past the circuit's table (the kernels verified against a clamped id): no such
+  // VerifierCircuitData, whatever the proof holds
+  if (c.key_id && c.key_id[p] >= (uint32_t)c.nkeys) st = -6;   // P2V_ERR_CIRCUIT
   results[p] = st;
   if (trace) {
     uint64_t* tr = trace + (int64_t)p * trace_words;

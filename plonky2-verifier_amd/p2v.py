@@ -146,6 +146,11 @@ def lib() -> ctypes.CDLL:
     L.p2v_proof_shape_json.argtypes = [ctypes.c_char_p, sz, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
     L.p2v_proof_shape_words.argtypes = [u64p, sz, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
     L.p2v_circuit_shape_variant.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(vp)]
+    L.p2v_vkey_from_json.argtypes = [vp, ctypes.c_char_p, sz, u64p]
+    L.p2v_circuit_with_keys.argtypes = [vp, u64p, sz, ctypes.POINTER(vp)]
+    L.p2v_circuit_num_keys.argtypes = [vp]
+    L.p2v_verifier_run_keyed.argtypes = [vp, u64p, vp, sz, i8p, u64p, vp, ctypes.c_uint32]
+    L.p2v_verify_batch_keyed.argtypes = [vp, u64p, vp, sz, i8p, ctypes.c_int]
     L.p2v_kernel_names.restype = ctypes.c_char_p
     L.p2v_last_error_message.restype = ctypes.c_char_p
     L.p2v_version.restype = ctypes.c_char_p
@@ -263,6 +268,44 @@ class VerifierCircuitData:
                 cache.popitem(last=False)
         return cache[key]
 
+    @property
+    def num_keys(self) -> int:
+        """Keys in the circuit's table (p2v_circuit_num_keys): 1 unless made by with_keys."""
+        n = lib().p2v_circuit_num_keys(self._h)
+        if n < 0:
+            _check(n)
+        return n
+
+    @property
+    def key_words(self) -> int:
+        """u64 words of one key in the key encoding (include/p2v.h): 4 * cap_len + 4."""
+        return 4 * (1 << self.info.cap_height) + 4
+
+    def vkey_words(self, vkey_json: Union[str, bytes]) -> np.ndarray:
+        """A VerifierOnlyCircuitData JSON (Types.hs:236-240) in the key encoding
+        (p2v_vkey_from_json): the cap digests, then circuit_digest."""
+        b = _bytes(vkey_json)
+        out = np.empty(self.key_words, dtype=np.uint64)
+        _check(lib().p2v_vkey_from_json(self._h, b, len(b), out.ctypes.data))
+        return out
+
+    def with_keys(self, vkeys) -> "VerifierCircuitData":
+        """The same common data with further verifier keys (p2v_circuit_with_keys): this
+        circuit's keys, then `vkeys` -- VerifierOnlyCircuitData JSON texts, word arrays in the
+        key encoding, or one [K, key_words] array.  Proof i of a keyed run (key_ids=) is verified
+        against key key_ids[i]; key 0 is the key this circuit was constructed with."""
+        if isinstance(vkeys, np.ndarray):
+            vkeys = list(vkeys.reshape(-1, self.key_words))
+        rows = [self.vkey_words(k) if isinstance(k, (str, bytes, bytearray)) else np.asarray(k, dtype=np.uint64).reshape(-1)
+                for k in vkeys]
+        for r in rows:
+            if r.size != self.key_words:
+                raise P2VError(E_ARG, f"a key has {r.size} words, the circuit's keys have {self.key_words}")
+        w = np.ascontiguousarray(np.concatenate(rows) if rows else np.empty(0, np.uint64), dtype=np.uint64)
+        h = ctypes.c_void_p()
+        _check(lib().p2v_circuit_with_keys(self._h, w.ctypes.data if rows else None, len(rows), ctypes.byref(h)))
+        return VerifierCircuitData(h.value)
+
     def for_proof(self, proof_json: Union[str, bytes]) -> "VerifierCircuitData":
         """The circuit (or its shape variant) whose layout holds this proof's public inputs and
         final polynomial as given (the reference reads both at any length)."""
@@ -348,6 +391,16 @@ class ProofWithPublicInputs:
         return cls(_bytes(text))
 
 
+def _key_ids(key_ids, n: int) -> Optional[np.ndarray]:
+    """key_ids= of the host entry points as a contiguous uint32 [n] array (None stays None)."""
+    if key_ids is None:
+        return None
+    ids = np.ascontiguousarray(key_ids, dtype=np.uint32).reshape(-1)
+    if ids.size != n:
+        raise P2VError(E_ARG, f"{ids.size} key ids for {n} proofs")
+    return ids
+
+
 def device_count() -> int:
     return int(lib().p2v_device_count())
 
@@ -364,19 +417,23 @@ class BatchVerifier:
         self._h = h
 
     def run(self, proofs: np.ndarray, trace: bool = False, unit_filters: bool = False, stream: int = 0,
-            tiled: bool = False):
+            tiled: bool = False, key_ids: Optional[np.ndarray] = None):
         """proofs: uint64 [n, proof_words] host array.  Returns int8 statuses (and trace).
         unit_filters: parity mode (P2V_FLAG_UNIT_FILTERS), statuses meaningless.  stream: a
         hipStream_t handle (0: the default stream).  tiled: the batch goes to the device in the
-        64-proof tiled layout (P2V_FLAG_INPUT_TILED; tiled here with tile_proofs)."""
+        64-proof tiled layout (P2V_FLAG_INPUT_TILED; tiled here with tile_proofs).  key_ids:
+        uint32 [n], proof i against key key_ids[i] of the circuit's table (with_keys;
+        p2v_verifier_run_keyed); None: every proof against key 0."""
         proofs = np.ascontiguousarray(proofs, dtype=np.uint64)
         n = proofs.shape[0]
         src = tile_proofs(proofs) if tiled else proofs
         res = np.empty(n, dtype=np.int8)
         tr = np.empty((n, self.circuit.info.trace_words), dtype=np.uint64) if trace else None
         flags = (FLAG_UNIT_FILTERS if unit_filters else 0) | (FLAG_INPUT_TILED if tiled else 0)
-        _check(lib().p2v_verifier_run(self._h, src.ctypes.data, n, res.ctypes.data,
-                                      tr.ctypes.data if trace else None, ctypes.c_void_p(stream) if stream else None, flags))
+        ids = _key_ids(key_ids, n)
+        _check(lib().p2v_verifier_run_keyed(self._h, src.ctypes.data, ids.ctypes.data if ids is not None else None, n,
+                                            res.ctypes.data, tr.ctypes.data if trace else None,
+                                            ctypes.c_void_p(stream) if stream else None, flags))
         return (res, tr) if trace else res
 
     @staticmethod
@@ -447,16 +504,18 @@ class BatchVerifier:
         return words, codes
 
     def run_device(self, proofs_ptr: int, n: int, results_ptr: int, stream: int = 0, trace_ptr: int = 0,
-                   sync: bool = True, tiled: bool = False, lookahead: bool = False) -> None:
+                   sync: bool = True, tiled: bool = False, lookahead: bool = False, key_ids: Optional[int] = None) -> None:
         """Device-resident batch: raw device pointers (e.g. torch tensor .data_ptr()) and a
         hipStream_t handle (torch.cuda.current_stream().cuda_stream).  tiled: the batch is in the
         64-proof tiled layout (P2V_FLAG_INPUT_TILED, tile_proofs).  lookahead: the batch is already
         complete in device memory, so its transcript may run ahead of this workspace's earlier
-        batches (P2V_FLAG_LOOKAHEAD)."""
+        batches (P2V_FLAG_LOOKAHEAD).  key_ids: the device pointer of n uint32 key ids
+        (p2v_verifier_run_keyed; under lookahead complete like the batch); None: key 0."""
         flags = (FLAG_INPUT_DEVICE | FLAG_RESULT_DEVICE | (0 if sync else FLAG_NO_SYNC) | (FLAG_INPUT_TILED if tiled else 0)
                  | (FLAG_LOOKAHEAD if lookahead else 0))
-        _check(lib().p2v_verifier_run(self._h, ctypes.c_void_p(proofs_ptr), n, ctypes.c_void_p(results_ptr),
-                                      ctypes.c_void_p(trace_ptr) if trace_ptr else None, ctypes.c_void_p(stream), flags))
+        _check(lib().p2v_verifier_run_keyed(self._h, ctypes.c_void_p(proofs_ptr), ctypes.c_void_p(key_ids) if key_ids else None, n,
+                                            ctypes.c_void_p(results_ptr), ctypes.c_void_p(trace_ptr) if trace_ptr else None,
+                                            ctypes.c_void_p(stream), flags))
 
     def last_timings(self) -> dict:
         buf = (ctypes.c_float * 16)()
@@ -726,14 +785,17 @@ def verify_batch_devices(vkey: VerifierCircuitData, packed: np.ndarray, devices:
     return res
 
 
-def verify_batch(vkey: VerifierCircuitData, packed: np.ndarray, device: int = 0) -> np.ndarray:
+def verify_batch(vkey: VerifierCircuitData, packed: np.ndarray, device: int = 0, key_ids: Optional[np.ndarray] = None) -> np.ndarray:
     """p2v_verify_batch: packed rows [n, proof_words] in host memory (pinned for the full link
     rate), verified by the circuit's pooled verifier on `device`, H2D copies overlapped with the
-    verification in chunks; int8 statuses."""
+    verification in chunks; int8 statuses.  key_ids: uint32 [n], proof i against key key_ids[i]
+    of the circuit's table (p2v_verify_batch_keyed); None: key 0."""
     packed = np.ascontiguousarray(packed, dtype=np.uint64)
     n = packed.shape[0]
     res = np.empty(n, dtype=np.int8)
-    _check(lib().p2v_verify_batch(vkey.handle, packed.ctypes.data, n, res.ctypes.data, device))
+    ids = _key_ids(key_ids, n)
+    _check(lib().p2v_verify_batch_keyed(vkey.handle, packed.ctypes.data, ids.ctypes.data if ids is not None else None, n,
+                                        res.ctypes.data, device))
     return res
 
 
