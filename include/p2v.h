@@ -369,7 +369,33 @@ int  p2v_verify_batch_devices(const p2v_circuit* c, const uint64_t* proofs, size
  *   ops 9-11: out[12i..] = the Poseidon permutation of a[12i..] in the latency forms of the
  *         transcript and the small-batch Merkle paths: 9 row (16 lanes per state), 10 quad
  *         (4 lanes), 11 pair (2 lanes)                     (Hash/Poseidon.hs:42-46)
- * Inputs may be any u64 (values >= p are congruent, as the reference reads them).
+ * Inputs of ops 0-11 may be any u64 (values >= p are congruent, as the reference reads them).
+ *
+ * Ops 12-20: the F / F^2 arithmetic and the FRI query code of k_fri and the vanishing kernels,
+ * each op the production function itself, one lane per item; a = n items of the stated words,
+ * out = n results, b = the op's shared words (NULL where none).  Field elements of a are
+ * canonical (< p): that is the contract of add, sub, neg, mul_small, emul and the inversions,
+ * and these ops do not widen it.
+ *   op 12: (x, y) -> add(x, y), sub(x, y), neg(x), mul_small(x, 7), mul_small(x, (uint32_t)y)
+ *          (Goldilocks.hs:105-133); 2 words -> 5
+ *   op 13: F^2 product (x.a, x.b, y.a, y.b) -> emul(x, y), through esqr(x) when y = x
+ *          (GoldilocksExt.hs:54-70); 4 words -> 2
+ *   op 14: x -> x^(p-2) by the addition chain, 0 -> 0 (Goldilocks.hs:155-156); 1 word -> 1
+ *   op 15: F^2 inverse, (0, 0) -> (0, 0) (invExt, GoldilocksExt.hs:76-80); 2 words -> 2
+ *   op 16: (u, v) -> 1/u, 1/v by one shared base-field inversion, with the fallback that keeps
+ *          inv 0 = 0 when either norm is 0; 4 words -> 4
+ *   op 17: e -> rootsOfUnity[k]^e, k = b[0] <= 32 shared, e < 2^32 per lane
+ *          (Goldilocks.hs:68-74); 1 word -> 1
+ *   op 18: x -> x^e in F^2, e = b[0] < 2^32 shared; 2 words -> 2
+ *   op 19: reduceWithPowers (Goldilocks.hs:180-183) as combineInitial runs it (Plonk/FRI.hs:151-207):
+ *          sum_v alpha^v y_v over the concatenation of up to 5 segments of the item's words.
+ *          b = 12 words: the item stride W, the segment count ns <= 5, 5 segment offsets (item
+ *          words), 5 segment lengths (every segment inside the item; those past ns ignored).
+ *          Item: alpha at words 0..1, base-field words y elsewhere; W words -> 2
+ *   op 20: one FRI folding step of arity 2^ab, ab = b[0] in 1..8, in the form the query kernel
+ *          takes at that arity (foldCosetWith, Plonk/FRI.hs:263-279).  Item: beta / ofs (F^2) at
+ *          words 0..1, then the 2^ab coset values (F^2) in received order; the twiddles and
+ *          1 / 2^ab are those of a circuit's step of that arity.  2 + 2 2^ab words -> 2
  * Test hook for the parity suite (edge values the synthetic proofs never produce). */
 int  p2v_selftest(int device, int op, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n);
 

@@ -53,6 +53,7 @@ extern "C" __global__ void k_vanish_final(DevCircuit);
 extern "C" __global__ void k_status(DevCircuit, int8_t*, uint64_t*, int64_t);
 extern "C" __global__ void k_selftest(int, const uint64_t*, const uint64_t*, uint64_t*, int64_t);
 extern "C" __global__ void k_selftest_forms(int, const uint64_t*, uint64_t*, int64_t);
+extern "C" __global__ void k_selftest_field(int, DevCircuit, const uint64_t*, uint64_t*);
 extern "C" __global__ void k_count_mismatches(const int8_t*, const int8_t*, int64_t, unsigned long long*);
 extern "C" __global__ void k_clock_probe(unsigned long long*);
 extern "C" __global__ void k_json_pack(const uint8_t*, const uint64_t*, int, const uint8_t*, int64_t, const int32_t*, int64_t, uint64_t*, int64_t, int8_t*);
@@ -1419,14 +1420,58 @@ int p2v_verifier_run_json(p2v_verifier* v, const char* blob, const uint64_t* off
   return run_packed(v, pack_json_into(v, blob, offsets, n, codes, n_device, stream_), n, results, codes, stream_);
 }
 
+// p2v_selftest ops 12-20: the field and FRI query code on items read as a proof batch is, through
+// a DevCircuit that holds the item array and the tables fill_scalars / fri_twiddles make for a
+// circuit with FRI arity bits 1..8 (step s = ab - 1).  b words, item words in and out per op;
+// the shared words are checked here, so the kernel reads nothing outside an item.
+static int selftest_field(int op, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n) {
+  static const size_t kB[9] = {0, 0, 0, 0, 0, 1, 1, 12, 1}, kIn[9] = {2, 4, 1, 2, 4, 1, 2, 0, 0}, kOut[9] = {5, 2, 1, 2, 4, 1, 2, 2, 2};
+  const size_t bw = kB[op - 12], wo = kOut[op - 12];
+  size_t w = kIn[op - 12];
+  if (bw && !b) return fail(P2V_E_ARG, "bad op / null argument");
+  if (op == 17 && b[0] > 32) return fail(P2V_E_ARG, "pow_root: k > 32");
+  if (op == 18 && b[0] > 0xFFFFFFFFull) return fail(P2V_E_ARG, "epow_u: e >= 2^32");
+  if (op == 19) {
+    w = (size_t)b[0];
+    bool ok = b[0] >= 2 && b[0] <= (1u << 20) && b[1] <= 5;
+    for (int k = 0; k < 5 && ok; k++) ok = b[2 + k] <= b[0] && b[7 + k] <= b[0] - b[2 + k];
+    if (!ok) return fail(P2V_E_ARG, "reduce_powers: segment table outside the item");
+  }
+  if (op == 20) {
+    if (b[0] < 1 || b[0] > 8) return fail(P2V_E_ARG, "fold: arity bits outside 1..8");
+    w = 2 + (2u << b[0]);
+  }
+  if (n > (size_t)INT32_MAX - 64) return fail(P2V_E_ARG, "too many items");
+  if (n == 0) return P2V_OK;
+  Circuit C;
+  C.arities = {1, 2, 3, 4, 5, 6, 7, 8};
+  C.step_depth.assign(8, 0); C.L.step_evals.assign(8, 0); C.L.step_path.assign(8, 0);
+  DevCircuit d{};
+  fill_scalars(C, d);
+  DevBuf da, db, dout, dtw;
+#define SCK(x) HCK_AS("p2v_selftest", x)
+  SCK(da.alloc(n * w * 8)); SCK(db.alloc(bw * 8)); SCK(dout.alloc(n * wo * 8));
+  SCK(upload(dtw, fri_twiddles(C), d.twiddles));
+  SCK(hipMemcpy(da.p, a, n * w * 8, hipMemcpyHostToDevice));
+  if (bw) SCK(hipMemcpy(db.p, b, bw * 8, hipMemcpyHostToDevice));
+  d.soa = (const uint64_t*)da.p; d.words = (int64_t)w; d.wstride = 1; d.tiled = 0;
+  d.n = (int32_t)n; d.B = (int32_t)((n + 63) / 64 * 64);
+  hipLaunchKernelGGL(k_selftest_field, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, op, d, (const uint64_t*)db.p, (uint64_t*)dout.p);
+  SCK(hipGetLastError());
+  SCK(hipMemcpy(out, dout.p, n * wo * 8, hipMemcpyDeviceToHost));
+#undef SCK
+  return P2V_OK;
+}
+
 int p2v_selftest(int device, int op, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n) {
   const bool needs_b = op == 0 || op == 3 || op == 4 || op == 6;
-  if (op < 0 || op > 11 || (n && (!a || !out || (needs_b && !b)))) return fail(P2V_E_ARG, "bad op / null argument");
+  if (op < 0 || op > 20 || (n && (!a || !out || (needs_b && !b)))) return fail(P2V_E_ARG, "bad op / null argument");
   const int ndev = p2v_device_count();
   if (ndev == 0) return fail(P2V_E_NODEVICE, "no HIP device");
   if (device < 0 || device >= ndev) return fail(P2V_E_ARG, "bad device index");
-  if (n == 0) return P2V_OK;
+  if (op < 12 && n == 0) return P2V_OK;
   HCK(hipSetDevice(device));
+  if (op >= 12) return selftest_field(op, a, b, out, n);
   // words per item of a / b and of out
   const bool scalar = op == 0 || op == 3 || op == 5 || op == 6 || op == 7 || op == 8;
   const size_t w = scalar ? 1 : 12, wo = op == 6 ? 2 : w;

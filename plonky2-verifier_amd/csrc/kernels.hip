@@ -1040,6 +1040,24 @@ __device__ __forceinline__ E reduce_powers(const DevCircuit& c, const Segs& S, i
   }
   return g;
 }
+// alpha^0..alpha^8 for reduce_powers
+__device__ __forceinline__ void alpha_powers(E alpha, E* ap) {
+  ap[0] = gl::eb(1); ap[1] = alpha;
+#pragma unroll
+  for (int k = 2; k <= 8; k++) ap[k] = gl::emul(ap[k - 1], alpha);
+}
+// one folding step of arity 2^ab: the form k_fri runs at each arity
+__device__ __forceinline__ E fold_step(const DevCircuit& c, int s, int ab, int64_t off, int p, E beta_over_ofs) {
+  E nv;
+  switch (ab) {
+    case 1: nv = fold_regs<1>(c, s, off, p, beta_over_ofs); break;
+    case 2: nv = fold_regs<2>(c, s, off, p, beta_over_ofs); break;
+    case 3: nv = fold_regs<3>(c, s, off, p, beta_over_ofs); break;
+    case 4: nv = fold16_halves(c, s, off, p, beta_over_ofs); break;
+    default: nv = fold_generic(c, s, ab, off, p, beta_over_ofs); break;
+  }
+  return nv;
+}
 
 // k_fri runs on the side stream beside k_merkle (see vanish.hip P2V_SIDE_WAVES): 5 waves per SIMD
 // caps it at 96 VGPRs, so a wave fits where one k_merkle wave retired (0: compiler default, 122)
@@ -1072,9 +1090,7 @@ extern "C" __global__ void __launch_bounds__(256) P2V_FRI_ATTR k_fri(DevCircuit 
   // leaf0 | leaf1 | leaf2[0, npp_all) | leaf3 | leaf2[npp_all, w2); secondBatch = leaf2[0, r') |
   // leaf2[npp_all, w2)
   E ap[9];
-  ap[0] = gl::eb(1); ap[1] = alpha;
-#pragma unroll
-  for (int k = 2; k <= 8; k++) ap[k] = gl::emul(ap[k - 1], alpha);
+  alpha_powers(alpha, ap);
   const int rr = r < npp_all ? r : npp_all;
   Segs s0{{l0, l1, l2, l3, l2 + npp_all}, {c.width[0], c.width[1], npp_all, c.width[3], c.width[2] - npp_all}, 5};
   Segs s1{{l2, l2 + npp_all, 0, 0, 0}, {rr, c.width[2] - npp_all, 0, 0, 0}, 2};
@@ -1105,15 +1121,7 @@ extern "C" __global__ void __launch_bounds__(256) P2V_FRI_ATTR k_fri(DevCircuit 
     const uint64_t ofs_inv = gl::mul(c.step_shift_inv[s], pow_root(c, logn, (0u - start) & nmask));
     const E beta = chal_e(c, CH_FRI_BETA(c) + 2 * s, p);
     const E bo = gl::escale(ofs_inv, beta);
-    E nv;
-    switch (ab) {
-      case 1: nv = fold_regs<1>(c, s, eoff, p, bo); break;
-      case 2: nv = fold_regs<2>(c, s, eoff, p, bo); break;
-      case 3: nv = fold_regs<3>(c, s, eoff, p, bo); break;
-      case 4: nv = fold16_halves(c, s, eoff, p, bo); break;
-      default: nv = fold_generic(c, s, ab, eoff, p, bo); break;
-    }
-    cur = nv;
+    cur = fold_step(c, s, ab, eoff, p, bo);
     idx >>= ab; logn -= ab;
   }
   qv[2 * (int64_t)c.B] = cur.a; qv[3 * (int64_t)c.B] = cur.b;
@@ -1261,5 +1269,57 @@ extern "C" __global__ void __launch_bounds__(256) k_selftest_forms(int op, const
     if (item < n)
 #pragma unroll
       for (int k = 0; k < 6; k++) o[6 * t + k] = x[k];
+  }
+}
+
+// The F / F^2 arithmetic and the FRI query code that k_fri and the vanishing kernels are built
+// from, on caller-chosen items (p2v_selftest ops 12-20, include/p2v.h).  One lane per item; the
+// items are read as k_fri reads a proof, through ld / lde on a DevCircuit whose batch is the item
+// array (c.soa, c.words the item stride, c.n items), so lanes past n re-read item n - 1; they store
+// nothing.  c carries the production tables of a circuit with FRI arity bits 1..8 (root_pow2,
+// twiddles and inv_arity of step s = ab - 1).  b: the op's shared words.
+extern "C" __global__ void __launch_bounds__(256) k_selftest_field(int op, DevCircuit c, const uint64_t* b, uint64_t* out) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int p = (int)i;
+  const bool live = i < c.n;
+  if (op == 12) {
+    const uint64_t x = ld(c, 0, p), y = ld(c, 1, p);
+    const uint64_t r[5] = {gl::add(x, y), gl::sub(x, y), gl::neg(x), gl::mul_small(x, 7), gl::mul_small(x, (uint32_t)y)};
+    if (live) for (int k = 0; k < 5; k++) out[5 * i + k] = r[k];
+  } else if (op == 13) {
+    const E x = lde(c, 0, p), y = lde(c, 2, p);
+    const E r = gl::eeq(x, y) ? gl::esqr(x) : gl::emul(x, y);
+    if (live) { out[2 * i] = r.a; out[2 * i + 1] = r.b; }
+  } else if (op == 14) {
+    const uint64_t r = inv_chain(ld(c, 0, p));
+    if (live) out[i] = r;
+  } else if (op == 15) {
+    const E r = einv(lde(c, 0, p));
+    if (live) { out[2 * i] = r.a; out[2 * i + 1] = r.b; }
+  } else if (op == 16) {
+    E iu, iv;
+    einv2(lde(c, 0, p), lde(c, 2, p), iu, iv);
+    if (live) { out[4 * i] = iu.a; out[4 * i + 1] = iu.b; out[4 * i + 2] = iv.a; out[4 * i + 3] = iv.b; }
+  } else if (op == 17) {
+    const uint64_t r = pow_root(c, (int)b[0], (uint32_t)ld(c, 0, p));
+    if (live) out[i] = r;
+  } else if (op == 18) {
+    const E r = epow_u(lde(c, 0, p), (uint32_t)b[0]);
+    if (live) { out[2 * i] = r.a; out[2 * i + 1] = r.b; }
+  } else if (op == 19) {
+    // b = item stride, segment count, 5 offsets (item words), 5 lengths; alpha at item words 0..1
+    Segs S;
+    S.ns = (int)b[1];
+    for (int k = 0; k < 5; k++) { S.off[k] = (int64_t)b[2 + k]; S.n[k] = (int)b[7 + k]; }
+    const E alpha = lde(c, 0, p);
+    E ap[9];
+    alpha_powers(alpha, ap);
+    const E r = reduce_powers(c, S, p, alpha, ap);
+    if (live) { out[2 * i] = r.a; out[2 * i + 1] = r.b; }
+  } else if (op == 20) {
+    // b[0] = arity bits ab; beta / ofs at item words 0..1, the 2^ab coset values after it
+    const int ab = (int)b[0];
+    const E r = fold_step(c, ab - 1, ab, 2, p, lde(c, 0, p));
+    if (live) { out[2 * i] = r.a; out[2 * i + 1] = r.b; }
   }
 }

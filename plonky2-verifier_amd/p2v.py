@@ -654,10 +654,19 @@ def device_selftest(op: int, a: np.ndarray, b: Optional[np.ndarray] = None, devi
     form), Poseidon permutation (op 1, a = [n, 12] states), 2-to-1 compression form (op 2, words
     8..11 taken as 0, words 0..3 returned), one MDS layer (op 4), the S-box forms (ops 5-8, x^7;
     op 6 the grouped pair (a[i], b[i]) -> out [n, 2]) and the latency forms of the permutation
-    (ops 9-11: row, quad, pair) on `device`."""
+    (ops 9-11: row, quad, pair) on `device`.  Ops 12-20: the F / F^2 arithmetic and the FRI query
+    code (a = [n, item words], b = the op's shared words, out = [n, result words]; see p2v.h)."""
     a = np.ascontiguousarray(a, dtype=np.uint64)
     n = a.shape[0]
-    out = np.zeros((n, 2), dtype=np.uint64) if op == 6 else np.zeros_like(a)   # op 4: b = [kl[12], kh[12]]
+    if 12 <= op <= 20:
+        win = {12: 2, 13: 4, 14: 1, 15: 2, 16: 4, 17: 1, 18: 2}.get(op)
+        if win is None:
+            win = int(b[0]) if op == 19 else 2 + (2 << int(b[0]))
+        if a.size != n * win:
+            raise ValueError(f"selftest op {op}: items of {win} words expected, got shape {a.shape}")
+        out = np.zeros((n, {12: 5, 14: 1, 16: 4, 17: 1}.get(op, 2)), dtype=np.uint64)
+    else:
+        out = np.zeros((n, 2), dtype=np.uint64) if op == 6 else np.zeros_like(a)   # op 4: b = [kl[12], kh[12]]
     bb = np.ascontiguousarray(b, dtype=np.uint64) if b is not None else None
     _check(lib().p2v_selftest(device, op, a.ctypes.data, bb.ctypes.data if bb is not None else None, out.ctypes.data, n))
     return out

@@ -134,6 +134,40 @@ def test_gpu_ext_conventions_vs_oracle(p2v, nb, mode, ext, arities):
     assert sts == [1, 1, -3, 0, 0][:len(cases)]
 
 
+@pytest.mark.parametrize("ext", [0, 1])
+@pytest.mark.parametrize("nb,arities", [(6, (5,)), (8, (5, 1)), (8, (6,)), (9, (8,))])
+def test_gpu_wide_arities_vs_oracle(p2v, nb, arities, ext):
+    """FRI arity bits 5..8 (circuit.cpp accepts 1..8; k_fri folds them by fold_generic, their
+    64..512-word step leaves go through leaf_hash_unit and the Merkle paths' row form): real
+    circuits under a Fixed strategy (ext 0) and under MinSize with fri_params arities (ext 1), at
+    the smallest degrees the generator can reach them (lde_bits >= the arity sum).  Valid proofs
+    accept, a corrupted step evaluation is -3 and a corrupted final polynomial 0; statuses and
+    full traces equal the oracle's (pinned at these shapes by test_verifier_literal.py) in latency
+    mode (4 proofs) and on the batch path with a ragged tail (the same rows repeated to 130);
+    (8, (5, 1)) also through the device byte packer."""
+    from support import proof_bytes
+    gc = gen_circuit(nb, 4, 0, 1, 28, 16, 0, 1, ext, arities)
+    cases = [gc.proof(1, 1), gc.proof(2, 2), gc.proof(1, 3, flags=1), gc.proof(1, 4, flags=2)]
+    sts, otrs = _gpu_vs_oracle(p2v, gc, cases, ext=ext)
+    assert sts == [1, 1, -3, 0]
+    vk = p2v.VerifierCircuitData.from_json(gc.common, gc.vkey, ext)
+    assert vk.info.step_arity_bits == tuple(arities)
+    packed = vk.pack_many(cases)
+    big = np.tile(packed, (33, 1))[:130]
+    bv = p2v.BatchVerifier(vk, 0, 130)
+    res, tr = bv.run(big, trace=True)
+    assert np.array_equal(res, np.tile(np.array(sts, dtype=np.int8), 33)[:130])
+    bad = np.nonzero((tr != np.tile(otrs, (33, 1))[:130]).any(axis=1))[0]
+    assert len(bad) == 0, bad[:10]
+    if arities == (5, 1):
+        bins = [proof_bytes(t, pi_prefix=bool(i % 2)) for i, t in enumerate(cases)]
+        words, codes = bv.pack_bytes(bins * 3)
+        assert not codes.any() and bv.last_bytes_device == 12
+        assert np.array_equal(words, np.tile(packed, (3, 1)))
+        res, codes = bv.run_bytes(bins * 3)
+        assert not codes.any() and list(res) == sts * 3
+
+
 RANDOMIZED = {
     "all": None,   # support.OPENING_KEYS
     "permutation": ("plonk_sigmas", "plonk_zs", "plonk_zs_next", "partial_products"),

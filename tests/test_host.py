@@ -460,7 +460,7 @@ def test_c_abi_argument_contract():
     arg_error("get_info circuit", L.p2v_circuit_get_info(None, ctypes.byref(inf)))
     arg_error("get_info info", L.p2v_circuit_get_info(c, None))
     arg_error("devices ndevices", L.p2v_verify_batch_devices(c, b, 1, b, dev0, 0, 0))
-    arg_error("selftest op", L.p2v_selftest(0, 12, b, b, b, 1))
+    arg_error("selftest op", L.p2v_selftest(0, 21, b, b, b, 1))
     # max_batch 0 is an argument error even where no device exists
     arg_error("create", L.p2v_verifier_create(c, 0, 0, ctypes.byref(out)))
     assert not out.value

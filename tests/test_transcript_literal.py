@@ -415,6 +415,43 @@ def test_fold16_in_halves_is_the_same_interpolant():
         assert eadd(emul(eadd(one, b8), lo), emul(esub(one, b8), hi)) == direct
 
 
+def fold_coset_lagrange(beta, arity_bits, offset, xs):
+    """foldCosetWith's value by Lagrange's formula instead of fold_coset's coefficient sums (which
+    take arity^2 modular powers: too slow from arity 128 on).  The interpolant of xs_j at the coset
+    points x_j = offset omega^j, at beta: with Z(X) = X^n - offset^n and Z'(x_j) = n x_j^(n-1) =
+    n offset^n / x_j, P(beta) = Z(beta) / (n offset^n) * sum_j xs_j x_j / (beta - x_j); where beta
+    is a coset point itself the value is that point's xs_j."""
+    n = 1 << arity_bits
+    omega = ROOTS[arity_bits]
+    pts, x = [], offset % P
+    for _ in range(n):
+        pts.append(x)
+        x = x * omega % P
+    if beta[1] == 0 and beta[0] in pts:
+        return xs[pts.index(beta[0])]
+    tot = (0, 0)
+    for xj, v in zip(pts, xs):
+        tot = eadd(tot, emul(escale(xj, v), einv(esub(beta, (xj, 0)))))
+    z = esub(epow(beta, n), (pow(offset, n, P), 0))
+    return escale(finv(n * pow(offset, n, P) % P), emul(z, tot))
+
+
+def test_fold_coset_lagrange_is_fold_coset():
+    """The Lagrange form the GPU fold tests use as their reference at arity bits >= 5 equals the
+    literal fold_coset for arity bits 1..5: random values, beta in F^2, in the base field, 0, and
+    on a coset point (exact integers)."""
+    import random
+    rng = random.Random(55)
+    for ab in range(1, 6):
+        n = 1 << ab
+        for t in range(6):
+            ofs = rng.randrange(1, P)
+            xs = [(rng.randrange(P), rng.randrange(P)) for _ in range(n)]
+            beta = [(rng.randrange(P), rng.randrange(P)), (rng.randrange(P), 0), (0, 0),
+                    (ofs * pow(ROOTS[ab], rng.randrange(n), P) % P, 0), (ofs, 0), (0, rng.randrange(P))][t]
+            assert fold_coset_lagrange(beta, ab, ofs, xs) == fold_coset(beta, ab, ofs, xs), (ab, t)
+
+
 def test_literal_transcript_and_fri_std_n12_two_folding_steps():
     """The standard recursion shape (degree_bits 12: two arity-16 folds, a 16-coefficient final
     polynomial), freshly generated: challenges and every per-query FRI value, literal vs oracle."""

@@ -74,3 +74,18 @@ def test_literal_verify_proof_mutation_campaign(lk, mode):
         seen.add(want)
     assert VLIT.verify_proof(common, vkey, json.loads(base)) == 1
     assert len(seen) >= 3, seen
+
+
+@pytest.mark.parametrize("nb,arities", [(6, (5,)), (8, (6,))])
+def test_literal_verify_proof_wide_arities(nb, arities):
+    """FRI arity bits 5 and 6 under a Fixed strategy (the shapes test_gpu's wide-arity tests
+    compare with the oracle): the literal verifier, which folds by the reference's own
+    O(arity^2) interpolation, gives the oracle's status on a valid proof and on one with a
+    corrupted step evaluation.  (9, (8,)) agrees as well but takes the literal verifier about a
+    minute per proof, so it is left out here."""
+    gc = gen_circuit(nb, 4, 0, 1, 28, 16, 0, 1, 0, arities)
+    common, vkey = json.loads(gc.common), json.loads(gc.vkey)
+    O = oracle()
+    for proof, want in ((gc.proof(1, 1), 1), (gc.proof(1, 3, flags=1), -3)):
+        assert O.verify_json(gc.common, gc.vkey, proof) == want
+        assert VLIT.verify_proof(common, vkey, json.loads(proof)) == want
