@@ -261,6 +261,35 @@ void p2v_verifier_free(p2v_verifier* v);
 int  p2v_verifier_run(p2v_verifier* v, const uint64_t* proofs, size_t n,
                       int8_t* results, uint64_t* trace, void* stream, uint32_t flags);
 
+/* Known openings of the constants/sigmas tree.  That tree belongs to the circuit (its cap is in
+ * the verifier key), so the leaf and sibling path opened at one index are the same words in every
+ * honest proof.  A circuit handle therefore carries, per device, a table of openings that a full
+ * Merkle check has already found True, direct-mapped by leaf index (no hashing, no eviction):
+ * 2^lde_bits rows of leaf_widths[0] + 4 (lde_bits - cap_height) words and a flag (standard
+ * circuit: 2^15 rows of 129 words, about 34 MB).  A later opening that equals its row word for
+ * word is accepted without hashing; any other takes the full check, and a True one is remembered.
+ * Exact memoisation: it NEVER changes a status or a trace, only time, and a handle warms across
+ * runs (uniform indices: 97 % of the rows after one 4096-proof batch, 99.9 % after two).  The
+ * table is made by the first p2v_verifier_create of the handle on a device, zero-filled, shared
+ * by all its workspaces there (concurrent streams included) and freed by p2v_circuit_free.
+ * Used by unkeyed runs of more than 64 proofs; keyed runs, smaller (latency-mode) runs and
+ * P2V_MERKLE_CSE=0 never touch it.  Read at p2v_verifier_create:
+ *   P2V_KNOWN_LEAVES   0: off (the launch sequence without the table); 1: on (default); 2: probe
+ *                      but never insert, so every opening misses: the cost of a cold table or a
+ *                      hostile batch, for measurement
+ *   P2V_KNOWN_MAX_MB   the table is made and used only if it fits (default 128, a policy value)
+ * HARD REQUIREMENT for P2V_FLAG_INPUT_DEVICE callers: the batch must not change from the call
+ * until the run has completed on its stream.  That was always the contract, but breaking it used
+ * to spoil only that run.  A remembered row is copied from the batch AFTER the opening was hashed
+ * from an earlier read of the same words, so words changed in between would be stored unhashed
+ * and accepted for the life of the circuit handle.  (Batches given in host memory are staged in
+ * a buffer of the workspace and cannot change.)
+ * p2v_circuit_known_stats: the handle's counters on `device` since the table was made, out[0]
+ * openings accepted from the table, out[1] openings that took the full check, out[2] rows
+ * inserted; all 0 where there is no table.  Synchronises the device and, like the verifier entry
+ * points, leaves `device` the calling thread's current device: tests and diagnostics only. */
+int  p2v_circuit_known_stats(const p2v_circuit* c, int device, uint64_t out[3]);
+
 /* p2v_verifier_run against the circuit's key table: proof i is verified against key key_ids[i]
  * (n entries; a device pointer exactly when P2V_FLAG_INPUT_DEVICE is set, else a host pointer,
  * copied through a staging buffer made by p2v_verifier_create: the run allocates nothing and

@@ -39,6 +39,8 @@ extern "C" __global__ void k_merkle_plan(DevCircuit);
 extern "C" __global__ void k_merkle_cse(DevCircuit);
 extern "C" __global__ void k_merkle_fix(DevCircuit);
 extern "C" __global__ void k_merkle_resolve(DevCircuit);
+extern "C" __global__ void k_merkle_known(DevCircuit);
+extern "C" __global__ void k_merkle_known_miss(DevCircuit);
 extern "C" __global__ void k_fri(DevCircuit);
 extern "C" __global__ void k_vanish_r2(DevCircuit);
 extern "C" __global__ void k_vanish_rn(DevCircuit);
@@ -80,9 +82,9 @@ int guarded(int other, F fn) {
 // (k_leaf + k_transcript: the two halves of k_phase1 as the lookahead path launches them).
 // Slot 0 is the retired transposing build's; it keeps its name and place (callers index by this
 // list) and is never recorded.
-const char* kKernelNames = "k_transpose,k_phase1,k_merkle,k_fri,k_vanish,k_status,k_vanish_final,k_lut,k_leaf,k_transcript";
+const char* kKernelNames = "k_transpose,k_phase1,k_merkle,k_fri,k_vanish,k_status,k_vanish_final,k_lut,k_leaf,k_transcript,k_merkle_known";
 enum Slot { SLOT_TRANSPOSE, SLOT_PHASE1, SLOT_MERKLE, SLOT_FRI, SLOT_VANISH, SLOT_STATUS, SLOT_VANISH_FINAL, SLOT_LUT, SLOT_LEAF,
-            SLOT_TRANSCRIPT, kNumKernels };   // the order of kKernelNames
+            SLOT_TRANSCRIPT, SLOT_KNOWN, kNumKernels };   // the order of kKernelNames
 
 // Device resources are owned by type: each owner is move-only and releases what it holds in its
 // destructor, on the device that is current then (p2v_verifier_free and pipe_free set it).
@@ -128,6 +130,13 @@ struct Event : Owned<hipEvent_t, hipEventDestroy> {
 }  // namespace
 
 struct HostPipe;
+// The circuit's known openings of tree 0 on one device (kernels.hip k_merkle_known): the rows, their
+// flags and the three counters.  Shared by every workspace of the circuit on that device; it warms
+// across runs and never affects a result, only time.
+struct KnownTable {
+  int device = -1;
+  DevBuf rows, valid, stat;
+};
 // The circuit handle also owns the verifiers the one-shot entry points (p2v_verify_batch,
 // p2v_verify_batch_devices) run on, kept across calls (a drop-in verifyProof
 // call must not re-create workspaces, streams and events).  Read-only for the circuit itself.
@@ -135,6 +144,8 @@ struct p2v_circuit {
   Circuit c;
   mutable std::mutex pool_mu;
   mutable std::vector<HostPipe*> pool;   // idle and busy pipes of every device
+  mutable std::mutex known_mu;
+  mutable std::vector<std::unique_ptr<KnownTable>> known;   // one per device, made by the first workspace that wants it
   ~p2v_circuit();
 };
 
@@ -202,6 +213,10 @@ struct p2v_verifier {
   int lane_min_batch = 16384;       // auto: lane form from this batch size on (env P2V_LANE_MIN)
   bool merkle_cse = true;           // shared Merkle nodes hashed once (env P2V_MERKLE_CSE=0: one full path per lane)
   bool cse_dirty = false;           // a run enqueued k_merkle_plan but not k_merkle_resolve
+  int known_mode = 1;               // known openings of tree 0 (env P2V_KNOWN_LEAVES: 0 off, 1 probe and insert,
+                                    // 2 probe only: every opening misses, the cold cost, measurement)
+  const KnownTable* known = nullptr;   // the circuit's table on this device (null: none, over P2V_KNOWN_MAX_MB or off)
+  bool known_dirty = false;         // a run enqueued k_merkle_known but not k_status
   int lat_max_batch = 64;           // latency mode (row-form Merkle paths, k_fri on its own stream) up to this
                                     // batch size (env P2V_LAT_MAX, measurement)
   bool single_stream = false;       // env P2V_SINGLE_STREAM=1: no side stream (measurement)
@@ -235,6 +250,7 @@ struct p2v_verifier {
   DevBuf kid;                       // staging for key ids given in host memory (p2v_verifier_run_keyed): Bmax u32
   DevBuf in, chal, chal2, leafdig, mk, fbits, qvals, van, vparts, lutre, lutpart, res, trace;
   DevBuf m_plan, m_fol, m_chain, m_count, m_fix, m_badq, m_node;   // shared-node Merkle paths (dev.h mcse)
+  DevBuf k_miss, k_missn;           // known openings: this workspace's miss list and its length
   DevBuf t_cs, t_kis, t_gkind, t_gpar, t_ggrp, t_gwoff, t_w, t_gs, t_ge, t_lin, t_lout, t_loff, t_llen, t_tw, t_ops, t_vit, t_rin, t_rout, t_roff, t_rch, t_pbase, t_pw;
   DevBuf j_blob, j_offs, j_skel, j_tok, j_ok;          // JSON / binary ingest, grown on demand
   DevBuf b_rsrc, b_rdst, b_rlen, b_coff, b_cval;       // the byte map
@@ -437,6 +453,7 @@ std::vector<int32_t> vanish_items(const Circuit& C, DevCircuit& d) {
 
 p2v_circuit::~p2v_circuit() {
   for (HostPipe* p : pool) pipe_free(p);
+  for (auto& k : known) { (void)hipSetDevice(k->device); k.reset(); }
 }
 
 extern "C" {
@@ -662,6 +679,7 @@ int p2v_verifier_create(const p2v_circuit* pc, int device, size_t max_batch, p2v
   if (const char* lm = getenv("P2V_LANE_MIN")) v->lane_min_batch = atoi(lm) > 0 ? atoi(lm) : v->lane_min_batch;
   if (const char* qm = getenv("P2V_QUAD_MIN")) v->quad_min_batch = atoi(qm) > 0 ? atoi(qm) : v->quad_min_batch;
   if (const char* mc = getenv("P2V_MERKLE_CSE")) v->merkle_cse = mc[0] != '0';
+  if (const char* kl = getenv("P2V_KNOWN_LEAVES")) v->known_mode = kl[0] == '0' ? 0 : kl[0] == '2' ? 2 : 1;
   if (const char* lx = getenv("P2V_LAT_MAX")) v->lat_max_batch = atoi(lx) >= 0 ? atoi(lx) : v->lat_max_batch;
   if (const char* tm = getenv("P2V_TRANSCRIPT")) v->transcript_mode = !strcmp(tm, "row") ? 1 : !strcmp(tm, "quad") ? 2 : !strcmp(tm, "lane") ? 3 : !strcmp(tm, "pair") ? 4 : 0;
   DevCircuit& d = v->dc;
@@ -721,6 +739,37 @@ int p2v_verifier_create(const p2v_circuit* pc, int device, size_t max_batch, p2v
     d.mplan = (uint32_t*)v->m_plan.p; d.mfol = (uint64_t*)v->m_fol.p; d.mchain = (uint32_t*)v->m_chain.p;
     d.mcount = (int32_t*)v->m_count.p; d.mfixn = d.mcount + nb * 16; d.mfix = (uint32_t*)v->m_fix.p;
     d.mbadq = (uint8_t*)v->m_badq.p; d.mnode = (uint64_t*)v->m_node.p;
+  }
+  // known openings of tree 0: with the shared-node paths only, and when the table fits its budget
+  // (P2V_KNOWN_MAX_MB, default 128: a policy value).  A leaf that is its own digest is not hashed.
+  d.nleaf = d.T;
+  d.kwords = d.lwidth[0] + 4 * d.depth0;
+  if (v->known_mode && d.mcse && !(d.noop_leaves && d.lwidth[0] <= 4)) {
+    size_t budget_mb = 128;
+    if (const char* mb = getenv("P2V_KNOWN_MAX_MB")) budget_mb = atoll(mb) > 0 ? (size_t)atoll(mb) : 0;
+    const size_t nrows = (size_t)1 << d.lde_bits;
+    const size_t bytes = nrows * ((size_t)d.kwords * 8 + 4);
+    if (bytes <= budget_mb << 20) {
+      std::lock_guard<std::mutex> lk(pc->known_mu);
+      for (auto& k : pc->known) if (k->device == device) v->known = k.get();
+      if (!v->known) {
+        auto k = std::make_unique<KnownTable>();
+        k->device = device;
+        ACK(k->rows.alloc(nrows * d.kwords * 8)); ACK(k->valid.alloc(nrows * 4)); ACK(k->stat.alloc(64));
+        ACK(hipMemset(k->rows.p, 0, nrows * d.kwords * 8)); ACK(hipMemset(k->valid.p, 0, nrows * 4)); ACK(hipMemset(k->stat.p, 0, 64));
+        ACK(hipStreamSynchronize(nullptr));   // the first run's stream does not wait for the null stream
+        v->known = k.get();
+        pc->known.push_back(std::move(k));
+      }
+    }
+    if (v->known) {
+      ACK(v->k_miss.alloc((size_t)d.Q * B * 4));
+      ACK(v->k_missn.alloc(64));
+      ACK(hipMemset(v->k_missn.p, 0, 64));   // then zeroed by each run's k_status
+      ACK(hipStreamSynchronize(nullptr));
+      d.krows = (uint64_t*)v->known->rows.p; d.kvalid = (uint32_t*)v->known->valid.p; d.kstat = (unsigned long long*)v->known->stat.p;
+      d.kmiss = (uint32_t*)v->k_miss.p; d.kmissn = (int32_t*)v->k_missn.p;
+    }
   }
   for (Event& x : v->ev) ACK(x.create_timed());
   v->timed = true;
@@ -834,7 +883,17 @@ int p2v_verifier_run_keyed(p2v_verifier* v, const uint64_t* proofs, const uint32
   else if (v->transcript_mode == 3) tl = 1;
   else if (v->transcript_mode == 4) tl = 2;
   const int nt_blocks = (tl * d.B + 255) / 256;
-  const int leaf_units = d.Q * d.T * NPB;
+  // Known openings of tree 0 (kernels.hip k_merkle_known): unkeyed runs above the latency mode with
+  // the shared-node paths.  Tree 0 then leaves the leaf units and the plan / chains / resolve; its
+  // statuses come from the probe and the miss kernel at the head of the side stream.
+  const bool lat = d.n <= v->lat_max_batch;
+  if (v->known && !key_ids && !lat && d.mcse) {
+    d.kmode = v->known_mode; d.kskip = 1;
+    int k = 0;
+    for (int j = 0; j < d.T; j++) if (v->dc.leaf_order[j] != 0) d.leaf_order[k++] = v->dc.leaf_order[j];
+    d.nleaf = k;
+  }
+  const int leaf_units = d.Q * d.nleaf * NPB;
   // staggered workspaces (p2v_verifier_chain): phase 1 after the linked workspace's latest one
   bool chained = false;   // read under the lock: chain links may change from other host threads
   {
@@ -880,7 +939,6 @@ int p2v_verifier_run_keyed(p2v_verifier* v, const uint64_t* proofs, const uint32
   // path, 4x shorter chains, 16x the lanes), one-wave work-groups for k_fri, and k_fri on a stream
   // of its own beside the vanishing kernels instead of after them.  Measured:
   // one proof 2.19 -> 1.98 ms, 64 proofs 2.18 -> 2.10 ms; at 128 proofs the row form's lanes cost more than its latency saves
-  const bool lat = d.n <= v->lat_max_batch;
   const int mk_wg = lat ? 64 : 256;
   const bool fri2 = lat && sd != st;
   if (fri2 && !v->side2) HCK(v->side2.create());
@@ -894,6 +952,20 @@ int p2v_verifier_run_keyed(p2v_verifier* v, const uint64_t* proofs, const uint32
   }
   // phase 2: Merkle paths on the main stream; FRI queries and the vanishing kernel (few,
   // long-latency waves) on the side stream, concurrently
+  if (d.kmode) {   // tree 0 from the table, first on the side stream (P2V_SINGLE_STREAM: in line); on the main stream
+                   // before k_merkle_plan it measured 2.4 % slower pipelined
+    // k_status zeroes the miss counter for the next run; a run that stopped in between leaves it to be zeroed here
+    if (v->known_dirty) HCK(hipMemsetAsync(v->k_missn.p, 0, 64, sd));
+    v->known_dirty = true;
+    T0(SLOT_KNOWN, sd);
+    k_merkle_known<<<(unsigned)(((int64_t)d.Q * d.n * 16 + 255) / 256), 256, 0, sd>>>(d);
+    DBG("k_merkle_known", sd);
+    // grid-stride over the miss list, as k_merkle_fix; at least one lane per opening of a full list
+    const unsigned miss_blocks = (unsigned)std::max<int64_t>(P2V_KNOWN_MISS_BLOCKS, ((int64_t)d.Q * d.n + 255) / 256);
+    k_merkle_known_miss<<<miss_blocks, 256, 0, sd>>>(d);
+    DBG("k_merkle_known_miss", sd);
+    T1(SLOT_KNOWN, sd);
+  }
   T0(SLOT_LUT, sd);
   if (d.n_lut_pieces > 0) k_lut<<<(d.r * d.n_lut_pieces * NPB + 3) / 4, 256, 0, sd>>>(d);
   DBG("k_lut", sd);
@@ -947,7 +1019,7 @@ int p2v_verifier_run_keyed(p2v_verifier* v, const uint64_t* proofs, const uint32
     v->cse_dirty = true;
     k_merkle_plan<<<(ncls * d.Q * NPB + P2V_PLAN_WAVES - 1) / P2V_PLAN_WAVES, 64 * P2V_PLAN_WAVES, 0, st>>>(d);
     DBG("k_merkle_plan", st);
-    const int64_t cse_waves = ((int64_t)d.T * d.Q * d.n + 63) / 64 + d.depth0 + 1;
+    const int64_t cse_waves = ((int64_t)(d.T - d.kskip) * d.Q * d.n + 63) / 64 + d.depth0 + 1;
     k_merkle_cse<<<(unsigned)((cse_waves + 31) / 32 * 8), 256, 0, st>>>(d);   // a multiple of 8 blocks (cse_wave: XCD ranges)
     DBG("k_merkle_cse", st);
     // grid-stride over the (usually empty) list: the latency form for up to 16 entries per block,
@@ -955,7 +1027,7 @@ int p2v_verifier_run_keyed(p2v_verifier* v, const uint64_t* proofs, const uint32
     // more batch); a larger grid waited ~0.5 ms per launch for free slots beside the other batch (r06e)
     k_merkle_fix<<<P2V_FIX_BLOCKS, 256, 0, st>>>(d);
     DBG("k_merkle_fix", st);
-    k_merkle_resolve<<<(merkle_units + 3) / 4, 256, 0, st>>>(d);
+    k_merkle_resolve<<<(d.Q * (d.T - d.kskip) * NPB + 3) / 4, 256, 0, st>>>(d);
     DBG("k_merkle_resolve", st);
     v->cse_dirty = false;
   } else k_merkle<<<(merkle_units + 3) / 4, 256, 0, st>>>(d);
@@ -967,6 +1039,7 @@ int p2v_verifier_run_keyed(p2v_verifier* v, const uint64_t* proofs, const uint32
   k_status<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(d, dres, dtrace, C.trace_words);
   DBG("k_status", st);
   T1(SLOT_STATUS, st);
+  v->known_dirty = false;
   // the challenge buffer's last reader is done (a run without the flag used buffer 0: a later
   // lookahead transcript into buffer 0 must wait for it as well)
   if (la) HCK(hipEventRecord(v->chal_free[la_slot], st));
@@ -1516,6 +1589,21 @@ int p2v_verifier_last_timings(const p2v_verifier* v, float* out, int max) {
   int k = 0;
   for (; k < kNumKernels && k < max; k++) out[k] = v->last_ms[k];
   return k;
+}
+
+int p2v_circuit_known_stats(const p2v_circuit* c, int device, uint64_t out[3]) {
+  if (!c || !out) return fail(P2V_E_ARG, "null argument");
+  out[0] = out[1] = out[2] = 0;
+  const KnownTable* k = nullptr;
+  {
+    std::lock_guard<std::mutex> lk(c->known_mu);
+    for (auto& t : c->known) if (t->device == device) k = t.get();
+  }
+  if (!k) return P2V_OK;
+  HCK(hipSetDevice(device));
+  HCK(hipDeviceSynchronize());
+  HCK(hipMemcpy(out, k->stat.p, 3 * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  return P2V_OK;
 }
 
 int p2v_verify_batch(const p2v_circuit* c, const uint64_t* proofs, size_t n, int8_t* results, int device) {

@@ -104,7 +104,22 @@ struct DevCircuit {
   uint32_t* mfix;                  // [mcap]: chain ids of the followers k_merkle_fix re-runs
   uint8_t* mbadq;                  // [T][Q][B]: the follower failed a shared-node check
   uint64_t* mnode;                 // [T][Q][4][B]: a follower's node at its meeting level
+  // Known openings of tree 0 (constants/sigmas: the circuit's tree, its cap in the verifier key),
+  // kernels.hip k_merkle_known / k_merkle_known_miss.  kmode of a run: 0 none (tree 0 with the other
+  // trees, as ever), 1 probe and insert, 2 probe only.  With kmode != 0, kskip = 1: the leaf units
+  // (leaf_order holds nleaf = T - 1 trees) and the shared-node kernels leave tree 0 out.
+  int32_t kmode, kskip, nleaf;
+  int32_t kwords;                  // words of a row: lwidth[0] + 4 depth0 (leaf, then siblings from level 0 up)
+  uint64_t* krows;                 // [2^lde_bits][kwords], per circuit and device; zero until inserted, then constant
+  uint32_t* kvalid;                // [2^lde_bits]: P2V_KNOWN_EMPTY / _VALID / _BUSY
+  unsigned long long* kstat;       // per circuit and device: hits, misses, rows inserted
+  uint32_t* kmiss;                 // [Q][B] of this workspace: the run's missed openings q << 22 | p
+  int32_t* kmissn;                 // entries of kmiss (k_status zeroes it for the next run)
 };
+#define P2V_KNOWN_EMPTY 0u
+#define P2V_KNOWN_VALID 1u
+#define P2V_KNOWN_BUSY 2u          // claimed by the one lane group that writes the row
+#define P2V_KNOWN_MISS_BLOCKS 256  // k_merkle_known_miss grid (as P2V_FIX_BLOCKS)
 #define P2V_CSE_MAX_DEPTH 12       // 5-bit follower fields of one u64 per owned level
 #define P2V_CSE_MAX_Q 31           // 5-bit query ids, 31 = none
 #define P2V_CSE_MAX_B (1 << 22)    // 22-bit proof index in a chain id

@@ -12,6 +12,8 @@
 //                 Hash/Sponge.hs:26-31) which do not depend on the challenges
 //   k_merkle      path compression (Hash/Merkle.hs:27-42) for the 4 initial trees and every
 //                 FRI step tree, one lane per (proof, query, tree)
+//   k_merkle_known, k_merkle_known_miss   tree 0 (the circuit's own) against the table of openings
+//                 already found True; only the openings not in it are hashed
 //   k_fri         combineInitial + folding steps + final polynomial, one lane per
 //                 (proof, query)  (Plonk/FRI.hs:151-407)
 //   k_status      reference evaluation order -> int8 status (+ optional trace)
@@ -25,16 +27,10 @@ using namespace p2d;
 using gl::E;
 
 // ------------------------------------------------------------------------ helpers
-__device__ __forceinline__ void leaf_hash_unit(const DevCircuit& c, int unit, int lane) {
-  const int NPB = c.B >> 6;
-  const int pb = unit % NPB, qt = unit / NPB;   // (position, query)-major: costly trees first
-  const int q = qt % c.Q, t = c.leaf_order[qt / c.Q];
-  const int p = pb * 64 + lane;
-  const int64_t base = c.q0 + (int64_t)q * c.qstride;
-  int64_t off; int len;
-  if (t < 4) { off = base + c.leaf[t]; len = c.lwidth[t]; }
-  else { int s = t - 4; off = base + c.step_evals[s]; len = 2 << c.arity[s]; }
-  uint64_t st[12];
+// The leaf sponge (Hash/Sponge.hs:26-31) of the len words at proof word off of lane p: st[0..3]
+// is the digest.  leaf_hash_unit calls it with a wave-uniform off, k_merkle_known_miss with the
+// lane's own.
+__device__ __forceinline__ void leaf_sponge(const DevCircuit& c, int64_t off, int len, int p, uint64_t (&st)[12]) {
 #pragma unroll
   for (int i = 0; i < 12; i++) st[i] = 0;
   if (c.noop_leaves && len <= 4) {   // P2V_EXT_HASH_OR_NOOP: plonky2 hash_or_noop, the leaf zero-padded
@@ -60,6 +56,18 @@ __device__ __forceinline__ void leaf_hash_unit(const DevCircuit& c, int unit, in
     const int nx = k - 8;
     p2::permute_dev<true>(st, i == 0, nx <= 0 ? 1 : (nx >= 8 ? 4 : ((7 << (nx >> 2)) & 7)));   // block 0: the folded zh round 0
   }
+}
+__device__ __forceinline__ void leaf_hash_unit(const DevCircuit& c, int unit, int lane) {
+  const int NPB = c.B >> 6;
+  const int pb = unit % NPB, qt = unit / NPB;   // (position, query)-major: costly trees first
+  const int q = qt % c.Q, t = c.leaf_order[qt / c.Q];   // (a run with known openings: the order without tree 0)
+  const int p = pb * 64 + lane;
+  const int64_t base = c.q0 + (int64_t)q * c.qstride;
+  int64_t off; int len;
+  if (t < 4) { off = base + c.leaf[t]; len = c.lwidth[t]; }
+  else { int s = t - 4; off = base + c.step_evals[s]; len = 2 << c.arity[s]; }
+  uint64_t st[12];
+  leaf_sponge(c, off, len, p, st);
   uint64_t* dst = c.leafdig + ((int64_t)(q * c.T + t) * 4) * c.B + p;
 #pragma unroll
   for (int i = 0; i < 4; i++) dst[(int64_t)i * c.B] = st[i];
@@ -368,7 +376,7 @@ __device__ __forceinline__ void phase1_body(const DevCircuit& c, int nt_blocks, 
     return;
   }
   const int unit = ((int)blockIdx.x - nt_blocks) * 4 + wave;
-  const int units = c.Q * c.T * (c.B >> 6);
+  const int units = c.Q * c.nleaf * (c.B >> 6);
   if (unit < units) leaf_hash_unit(c, unit, lane);
 }
 extern "C" __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) k_phase1(DevCircuit c, int nt_blocks, int tl) {
@@ -434,7 +442,7 @@ extern "C" __global__ void __launch_bounds__(256) k_transcript_pair_keyed(DevCir
 }
 extern "C" __global__ void __launch_bounds__(256) k_leaf(DevCircuit c) {
   const int unit = (int)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (unit < c.Q * c.T * (c.B >> 6)) leaf_hash_unit(c, unit, threadIdx.x & 63);
+  if (unit < c.Q * c.nleaf * (c.B >> 6)) leaf_hash_unit(c, unit, threadIdx.x & 63);
 }
 
 // ------------------------------------------------------------------------ Merkle paths
@@ -563,7 +571,9 @@ extern "C" __global__ void __launch_bounds__(64 * P2V_PLAN_WAVES) k_merkle_plan(
   const bool live = unit_live && p < c.n;
   int sh, depth;
   class_shape(c, cls, sh, depth);
-  const int ntr = cls == 0 ? 4 : 1, t0 = cls == 0 ? 0 : 3 + cls;
+  // class 0: the initial trees, without tree 0 in a run with known openings (kskip = 1: its
+  // statuses are k_merkle_known's and k_merkle_known_miss's alone)
+  const int ntr = cls == 0 ? 4 - c.kskip : 1, t0 = cls == 0 ? c.kskip : 3 + cls;
   int e = 0, loc = 0, cnt = 0;
   if (live) {
     const uint64_t* qi = c.chal + (int64_t)CH_QIDX(c) * c.B + p;
@@ -830,9 +840,9 @@ extern "C" __global__ void __launch_bounds__(256) k_merkle_resolve(DevCircuit c)
   const int lane = threadIdx.x & 63;
   const int unit = blockIdx.x * 4 + (threadIdx.x >> 6);
   const int NPB = c.B >> 6;
-  if (unit >= c.Q * c.T * NPB) return;
+  if (unit >= c.Q * (c.T - c.kskip) * NPB) return;
   const int pb = unit % NPB, qt = unit / NPB;
-  const int q = qt % c.Q, t = qt / c.Q;
+  const int q = qt % c.Q, t = qt / c.Q + c.kskip;   // (known openings: trees 1 .. T - 1)
   const int p = pb * 64 + lane;
   if (p >= c.n) return;
   const int cls = tree_class(t);
@@ -852,6 +862,167 @@ extern "C" __global__ void __launch_bounds__(256) k_merkle_resolve(DevCircuit c)
   uint8_t* mk = c.mk_ok + (int64_t)t * c.B + p;
   const int64_t qs = (int64_t)c.T * c.B;
   mk[q * qs] = mk[a * qs];
+}
+
+// ------------------------------------------------------------------------ known openings of tree 0
+// Tree 0 (constants/sigmas) belongs to the circuit, not to the proof: its cap is in the verifier
+// key (Plonk/FRI.hs:105-117), so the leaf and the sibling path opened at index idx are the same
+// words in every honest proof of the circuit.  The Merkle check is a pure function of (cap, idx,
+// leaf words, sibling words) and the cap is fixed per circuit, so an input that evaluated to True
+// once is True for ever: the circuit keeps, per device, a table direct-mapped by idx of inputs that
+// the full computation below found True, and an opening whose kwords words equal row idx word for
+// word is accepted without hashing.  Exact memoisation: nothing is assumed of the hash, and an
+// opening that differs from the row in one word (or meets an empty row) takes the reference
+// computation.  Unkeyed runs above the latency mode with shared-node paths only (api.cpp).
+//   k_merkle_known       16 lanes per (query, proof): flag, then the row against the proof's
+//                        words; loads and compares only.  Hit: mk_ok = 1.  Miss: listed
+//   k_merkle_known_miss  the listed openings in full (leaf sponge, path, cap entry); a True one is
+//                        inserted (kmode 1)
+// Ordering.  A row goes EMPTY -> BUSY -> VALID once and is never written again: the lane group
+// whose compare-and-swap took it from EMPTY writes the words, fences at device scope, and stores
+// VALID with release at agent scope; a reader loads the flag with acquire at agent scope before it
+// reads a word.  So a reader that sees VALID sees the final words, and every other view (EMPTY,
+// BUSY, a flag that some lanes of the group see later than others) is a miss: a stale or torn view
+// can only cost the computation, never accept an opening.  Runs of other workspaces on other
+// streams read and fill the same table concurrently under the same rule.
+extern "C" __global__ void __launch_bounds__(256) k_merkle_known(DevCircuit c) {
+  const int lane = threadIdx.x & 63, L = threadIdx.x & 15;
+  const int64_t g = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 4;   // the opening: proofs fastest
+  const bool live = g < (int64_t)c.Q * c.n;
+  const int64_t gg = live ? g : 0;
+  const int p = (int)(gg % c.n), q = (int)(gg / c.n);
+  const uint32_t idx = (uint32_t)chal(c, CH_QIDX(c) + q, p);   // < 2^lde_bits: masked by the transcript
+  const int64_t base = c.q0 + (int64_t)q * c.qstride;
+  const int lw = c.lwidth[0];
+  bool bad = !live;
+  if (live) {
+    bad = __hip_atomic_load(c.kvalid + idx, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) != P2V_KNOWN_VALID;
+    if (!bad) {
+      const uint64_t* row = c.krows + (int64_t)idx * c.kwords;   // lane L: words L, L + 16, ...: 128-B reads of the row
+#pragma unroll 3
+      for (int j = L; j < c.kwords; j += 16)
+        bad |= row[j] != ld(c, j < lw ? base + c.leaf[0] + j : base + c.path[0] + (j - lw), p);
+    }
+  }
+  const bool miss = live && ((__ballot(bad) >> (lane & 48)) & 0xFFFFu) != 0;   // any lane of the group
+  // the wave's misses are adjacent in the list (a dense list stays in proof order): one atomic per wave
+  const uint64_t mm = __ballot(miss && L == 0);
+  bool listed = false;
+  if (mm) {
+    int at = 0;
+    if (lane == 0) at = atomicAdd(c.kmissn, __popcll(mm));
+    at = __shfl(at, 0);
+    const int64_t pos = (int64_t)at + __popcll(mm & ((1ULL << lane) - 1));
+    listed = pos < (int64_t)c.Q * c.B;   // (always: one entry per opening of the run)
+    if (miss && L == 0 && listed) c.kmiss[pos] = (uint32_t)q << 22 | (uint32_t)p;
+  }
+  // a miss is k_merkle_known_miss's to decide; one that could not be listed is rejected
+  if (live && L == 0 && (!miss || !listed)) c.mk_ok[(int64_t)(q * c.T) * c.B + p] = miss ? 0 : 1;
+}
+// the row of a True opening: by the one group (or lane, nl = 1) that takes it from EMPTY
+__device__ __forceinline__ void known_insert(const DevCircuit& c, uint32_t idx, int q, int p, int L, int nl, bool mine) {
+  const int64_t base = c.q0 + (int64_t)q * c.qstride;
+  const int lw = c.lwidth[0];
+  if (mine) {
+    uint64_t* row = c.krows + (int64_t)idx * c.kwords;
+    for (int j = L; j < c.kwords; j += nl) row[j] = ld(c, j < lw ? base + c.leaf[0] + j : base + c.path[0] + (j - lw), p);
+  }
+  // each lane's words are complete at device scope after its own fence; the group's lanes then
+  // report through a ballot, and lane 0 stores the flag only on every lane's report, so the flag
+  // store depends on all the group's fences, not on the wave's lanes running in step (see
+  // "Ordering" above)
+  __threadfence();
+  const int lane = threadIdx.x & 63;
+  const uint64_t grp = nl == 1 ? 1ULL << lane : 0xFFFFULL << (lane & 48);
+  const uint64_t done = __ballot(mine);
+  if (mine && L == 0 && (done & grp) == grp) {
+    __hip_atomic_store(c.kvalid + idx, P2V_KNOWN_VALID, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+    atomicAdd(c.kstat + 2, 1ULL);
+  }
+}
+// one listed opening in the lane form: the reference computation as k_phase1's leaf unit and
+// k_merkle's path run it
+__device__ __forceinline__ void known_miss_lane(const DevCircuit& c, int64_t k) {
+  const uint32_t id = c.kmiss[k];
+  const int q = (int)(id >> 22), p = (int)(id & 0x3FFFFFu);
+  const int64_t base = c.q0 + (int64_t)q * c.qstride;
+  const uint32_t idx0 = (uint32_t)chal(c, CH_QIDX(c) + q, p);
+  uint64_t st[12];
+  leaf_sponge(c, base + c.leaf[0], c.lwidth[0], p, st);
+  uint64_t cur[4] = {st[0], st[1], st[2], st[3]};
+  uint32_t idx = idx0;
+  for (int l = 0; l < c.depth0; l++) {
+    uint64_t sib[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) sib[i] = ld(c, base + c.path[0] + 4 * l + i, p);
+    merkle_level(cur, sib, idx & 1u);
+    idx >>= 1;
+  }
+  const bool ok = cap_ok(c, 0, idx, cur, p);
+  c.mk_ok[(int64_t)(q * c.T) * c.B + p] = ok ? 1 : 0;
+  const bool mine = ok && c.kmode == 1 && atomicCAS(c.kvalid + idx0, P2V_KNOWN_EMPTY, P2V_KNOWN_BUSY) == P2V_KNOWN_EMPTY;
+  known_insert(c, idx0, q, p, 0, 1, mine);
+}
+// Like k_merkle_fix: the row form of the permutation for a short list (the usual one: the few
+// openings of a warm batch that are new or wrong are on the batch's critical path), one lane per
+// entry for a long one (a cold table, a batch of garbage)
+extern "C" __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))) k_merkle_known_miss(DevCircuit c) {
+  __shared__ TLdsAny T;
+  const int64_t nmiss = min((int64_t)*c.kmissn, (int64_t)c.Q * c.B);
+  if (blockIdx.x == 0 && threadIdx.x == 0) {   // every opening of the run was probed once
+    atomicAdd(c.kstat, (unsigned long long)((int64_t)c.Q * c.n - nmiss));
+    atomicAdd(c.kstat + 1, (unsigned long long)nmiss);
+  }
+  if (nmiss > (int64_t)gridDim.x * 64) {   // more than 4 passes of the latency rows: one lane per entry (grid-uniform)
+    const int64_t lanes = (int64_t)gridDim.x * 256;
+    for (int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x; k < nmiss; k += lanes) known_miss_lane(c, k);
+    return;
+  }
+  if ((int64_t)blockIdx.x * 16 >= nmiss) return;   // block-uniform: no entry for this block's rows
+  tlds_fill_form(T, 16);
+  __builtin_amdgcn_s_setprio(3);
+  lp::Row LR;
+  lp::init(LR, T.l, threadIdx.x);
+  const lp::TLdsL& TL = T.l;
+  const int L = LR.L;
+  const int lw = c.lwidth[0];
+  const int64_t rows = (int64_t)gridDim.x * 16;
+  for (int64_t k = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 4; k < nmiss; k += rows) {   // row-uniform
+    const uint32_t id = c.kmiss[k];
+    const int q = (int)(id >> 22), p = (int)(id & 0x3FFFFFu);
+    const int64_t base = c.q0 + (int64_t)q * c.qstride;
+    const uint32_t idx0 = (uint32_t)chal(c, CH_QIDX(c) + q, p);
+    // the leaf sponge (Hash/Sponge.hs:26-31; overwrite mode, no padding): lane L < 8 takes word
+    // i + L of each block, the other state words stay
+    uint64_t x = 0;
+    for (int i = 0; i < lw; i += 8) {
+      if (L < 8 && i + L < lw) x = ld(c, base + c.leaf[0] + i + L, p);
+      x = lp::permute(x, LR, TL);
+    }
+    uint64_t cur = L < 4 ? x : 0;
+    uint32_t idx = idx0;
+    for (int l = 0; l < c.depth0; l++) {   // as k_merkle_row
+      const uint64_t sib = L < 8 ? ld(c, base + c.path[0] + 4 * l + (L & 3), p) : 0;
+      const uint64_t c0 = rp::get_word(cur, 0), c1 = rp::get_word(cur, 1), c2 = rp::get_word(cur, 2), c3 = rp::get_word(cur, 3);
+      const uint64_t cb = L == 4 ? c0 : L == 5 ? c1 : L == 6 ? c2 : c3;
+      const bool odd = idx & 1u;
+      const uint64_t y = L < 4 ? (odd ? sib : cur) : L < 8 ? (odd ? cb : sib) : 0;
+      cur = lp::permute(y, LR, TL);
+      idx >>= 1;
+    }
+    bool ok = idx < (uint32_t)c.cap_len;
+    const uint32_t ci = ok ? idx : 0;
+    const uint64_t root = L < 4 ? c.cs_cap[ci * 4 + L] : 0;   // unkeyed runs only: key 0's cap
+    const uint64_t eq = (L >= 4 || root == cur) ? 1 : 0;
+    ok = ok && (rp::get_word(eq, 0) & rp::get_word(eq, 1) & rp::get_word(eq, 2) & rp::get_word(eq, 3));
+    if (L == 0) c.mk_ok[(int64_t)(q * c.T) * c.B + p] = ok ? 1 : 0;
+    if (ok && c.kmode == 1) {   // row-uniform
+      uint32_t old = P2V_KNOWN_VALID;
+      if (L == 0) old = atomicCAS(c.kvalid + idx0, P2V_KNOWN_EMPTY, P2V_KNOWN_BUSY);
+      old = (uint32_t)rp::get_word((uint64_t)old, 0);
+      known_insert(c, idx0, q, p, L, 16, old == P2V_KNOWN_EMPTY);
+    }
+  }
 }
 
 // Latency mode (small batches, api.cpp): the same paths in the row form of the permutation
@@ -1141,6 +1312,7 @@ extern "C" __global__ void __launch_bounds__(256) k_status(DevCircuit c, int8_t*
                                                            int64_t trace_words) {
   // a few short waves that gate the workspace's next batch: ahead of co-resident phase-1 waves
   __builtin_amdgcn_s_setprio(3);
+  if (c.kmode && blockIdx.x == 0 && threadIdx.x == 0) *c.kmissn = 0;   // the next run's (its readers joined before this launch)
   const int p = blockIdx.x * 256 + threadIdx.x;
   if (p >= c.n) return;
   const bool eqs_ok = c.van[p] != 0;

@@ -149,6 +149,7 @@ def lib() -> ctypes.CDLL:
     L.p2v_vkey_from_json.argtypes = [vp, ctypes.c_char_p, sz, u64p]
     L.p2v_circuit_with_keys.argtypes = [vp, u64p, sz, ctypes.POINTER(vp)]
     L.p2v_circuit_num_keys.argtypes = [vp]
+    L.p2v_circuit_known_stats.argtypes = [vp, ctypes.c_int, u64p]
     L.p2v_verifier_run_keyed.argtypes = [vp, u64p, vp, sz, i8p, u64p, vp, ctypes.c_uint32]
     L.p2v_verify_batch_keyed.argtypes = [vp, u64p, vp, sz, i8p, ctypes.c_int]
     L.p2v_kernel_names.restype = ctypes.c_char_p
@@ -275,6 +276,14 @@ class VerifierCircuitData:
         if n < 0:
             _check(n)
         return n
+
+    def known_stats(self, device: int = 0) -> dict:
+        """The handle's known-openings counters on `device` (p2v_circuit_known_stats: openings of
+        the constants/sigmas tree accepted from the table, openings that took the full check, rows
+        inserted); zeros where there is no table.  Synchronises the device: tests and diagnostics."""
+        out = np.zeros(3, dtype=np.uint64)
+        _check(lib().p2v_circuit_known_stats(self._h, device, out.ctypes.data))
+        return {"hits": int(out[0]), "misses": int(out[1]), "inserted": int(out[2])}
 
     @property
     def key_words(self) -> int:
