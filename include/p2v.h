@@ -221,6 +221,69 @@ int  p2v_vkey_from_json(const p2v_circuit* c, const char* vkey_json, size_t len,
 int  p2v_circuit_with_keys(const p2v_circuit* base, const uint64_t* key_words, size_t nkeys, p2v_circuit** out);
 int  p2v_circuit_num_keys(const p2v_circuit* c);
 
+/* ---- gate programs: constraints of gates the library does not know (host-only) ----------
+ * The reference knows 16 gate kinds; any other string of common.gates is an UnknownGate and the
+ * circuit is refused (Gate/Constraints.hs:108; P2V_E_CIRCUIT here).  Its own gates are
+ * straight-line programs over Expr (Algebra/Expr.hs:28-35, Gate/Computation.hs:34-36, :157-165),
+ * and a caller may hand libp2v such a program for a gate string of its own.  Opt-in, like
+ * P2V_EXT_*: without programs every entry point behaves as before, and the reference has no such
+ * gate, so its parity is pinned by the tests' restatements of the built-in gates only.
+ * Encoding (version 1): P2V_WORDS_GATE_MAGIC, the number of instructions, then per instruction
+ * its opcode and operands, one u64 each:
+ *   0 WIRE k    local_wires ! k                 (WireV)    4 ADD a b   a + b in F^2   (AddE)
+ *   1 CONST k   local_constants ! k             (ConstV)   5 SUB a b   a - b          (SubE)
+ *   2 PIHASH k  fromBase (public_inputs_hash !! k), k < 4  6 MUL a b   a * b          (MulE)
+ *   3 LIT x     fromBase (x mod p), any u64     (LitE)     7 IMG a     (0, 1) * a     (ImgE)
+ *   8 COMMIT a  no value; a is the gate's next constraint  (Commit)
+ * Ops 0-7 define the values 0, 1, 2, ... in order of appearance; a and b are numbers of earlier
+ * values (SSA, straight-line).  The committed values, in order, are the gate's constraints: they
+ * are multiplied by the gate's selector filter and enter the alpha-combination exactly as a
+ * built-in gate's do (Plonk/Vanishing.hs:113-125).  Selector variables are not readable.
+ * Limits of this build (beyond them: P2V_E_CIRCUIT): P2V_GATE_PROGRAM_MAX_INSTRS instructions,
+ * and P2V_GATE_PROGRAM_MAX_LIVE results of ADD / SUB / MUL / IMG alive at once (a result is alive
+ * from its instruction to its last use; WIRE / CONST / PIHASH / LIT values occupy nothing).
+ * Cost: a program gate is interpreted, one wave per 64 proofs, about 0.5 us per instruction of
+ * the longest program (a latency chain beside the Merkle kernels, not throughput).  Measured on
+ * the 4096-proof degree_bits-12 recursion circuit with all twelve restated built-in gates as
+ * programs, PoseidonGate's 5 109 instructions among them: the vanishing slot of
+ * a serial pass 0.35 -> 2.71 ms, pipelined throughput 0.72 of the hand-written kernels'.  A
+ * circuit without program gates launches nothing new and costs nothing.
+ *   p2v_circuit_from_json_gates / _from_words_gates: as the _ex constructors, with program
+ *     progs[i] used for every gate whose string equals progs[i].gate byte for byte (word
+ *     encoding: the UnknownGate's name).  nprogs == 0 is the _ex call.  An unknown gate without
+ *     a program stays P2V_E_CIRCUIT; a program no gate uses is ignored.  P2V_E_PARSE: bad magic,
+ *     truncated or over-long encoding, unknown opcode, operand that is not an earlier value.
+ *     P2V_E_CIRCUIT: WIRE index >= num_wires, CONST index >= config.num_constants, PIHASH index
+ *     >= 4, or a used program beyond the limits.  P2V_E_ARG: two programs with one string, or a
+ *     string that parses as a built-in gate (a program never overrides one).  Shape variants and
+ *     p2v_circuit_with_keys keep the programs.
+ *   p2v_circuit_num_program_gates: gates of the circuit that are evaluated by a program.
+ *   p2v_gate_program_eval: the host statement of the semantics.  wires / consts: nwires / nconsts
+ *     F^2 values (re, im), pih: 4 F; out receives the constraints (re, im each), at most maxout.
+ *     Returns their number, or P2V_E_PARSE / P2V_E_CIRCUIT as above (indices against nwires /
+ *     nconsts), P2V_E_ARG when there are more than maxout.  Row words are field elements as a
+ *     packed proof holds them, canonical (< p); the evaluator reduces a word that is not, the
+ *     device (which only ever reads packed proofs, and p2v_selftest op 21 items) does not.
+ *   p2v_gate_program_info: what the library makes of an encoding, without a circuit: info[0] the
+ *     instructions, info[1] the constraints (COMMITs), info[2] the values, info[3] the results
+ *     alive at once = the slots the device interpreter's lowering assigns (against
+ *     P2V_GATE_PROGRAM_MAX_LIVE).  P2V_E_PARSE as above; the limits are not applied. */
+#define P2V_WORDS_GATE_MAGIC 0x5032564700000001ULL   /* "P2VG", version 1 */
+#define P2V_GATE_PROGRAM_MAX_INSTRS 16384
+#define P2V_GATE_PROGRAM_MAX_LIVE   32
+typedef struct p2v_gate_program {
+  const char* gate; size_t gate_len;       /* the exact string of common.gates[i] */
+  const uint64_t* words; size_t nwords;    /* the encoding above */
+} p2v_gate_program;
+int  p2v_circuit_from_json_gates(const char* common_json, size_t common_len, const char* vkey_json, size_t vkey_len,
+                                 uint32_t ext, const p2v_gate_program* progs, size_t nprogs, p2v_circuit** out);
+int  p2v_circuit_from_words_gates(const uint64_t* words, size_t n, uint32_t ext,
+                                  const p2v_gate_program* progs, size_t nprogs, p2v_circuit** out);
+int  p2v_circuit_num_program_gates(const p2v_circuit* c);
+int  p2v_gate_program_eval(const uint64_t* words, size_t nwords, const uint64_t* wires, int nwires,
+                           const uint64_t* consts, int nconsts, const uint64_t pih[4], uint64_t* out, int maxout);
+int  p2v_gate_program_info(const uint64_t* words, size_t nwords, int64_t info[4]);
+
 /* ---- verification (GPU) ------------------------------------------------------------ */
 #define P2V_FLAG_INPUT_DEVICE  1u /* `proofs` is a device pointer on the verifier's device  */
 #define P2V_FLAG_RESULT_DEVICE 2u  /* `results` (and trace) are device pointers              */
@@ -425,6 +488,13 @@ int  p2v_verify_batch_devices(const p2v_circuit* c, const uint64_t* proofs, size
  *          takes at that arity (foldCosetWith, Plonk/FRI.hs:263-279).  Item: beta / ofs (F^2) at
  *          words 0..1, then the 2^ab coset values (F^2) in received order; the twiddles and
  *          1 / 2^ab are those of a circuit's step of that arity.  2 + 2 2^ab words -> 2
+ *   op 21: the gate-program interpreter of the vanishing kernels (k_vanish_prog_*, "gate
+ *          programs" above) on caller-chosen rows.  b = nwires, nconsts, then the program's words
+ *          (read up to the end its instruction count implies and checked as at circuit creation;
+ *          like the other ops' shared words, a b that does not pass is P2V_E_ARG, decided before
+ *          any device call).  The item's field elements are canonical (< p), as for ops 12-20.  Item: the nwires wires, then the nconsts constants, as F^2
+ *          values (re, im), then the 4 public-inputs-hash words; 2 (nwires + nconsts) + 4 words
+ *          -> 2 words per constraint (re, im), in commit order
  * Test hook for the parity suite (edge values the synthetic proofs never produce). */
 int  p2v_selftest(int device, int op, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n);
 

@@ -50,6 +50,9 @@ extern "C" __global__ void k_vanish_coset_r2(DevCircuit);
 extern "C" __global__ void k_vanish_coset_rn(DevCircuit);
 extern "C" __global__ void k_vanish_lookup_r2(DevCircuit);
 extern "C" __global__ void k_vanish_lookup_rn(DevCircuit);
+extern "C" __global__ void k_vanish_prog_r2(DevCircuit);
+extern "C" __global__ void k_vanish_prog_rn(DevCircuit);
+extern "C" __global__ void k_selftest_prog(DevCircuit, uint64_t*, int);
 extern "C" __global__ void k_lut(DevCircuit);
 extern "C" __global__ void k_vanish_final(DevCircuit);
 extern "C" __global__ void k_status(DevCircuit, int8_t*, uint64_t*, int64_t);
@@ -251,7 +254,7 @@ struct p2v_verifier {
   DevBuf in, chal, chal2, leafdig, mk, fbits, qvals, van, vparts, lutre, lutpart, res, trace;
   DevBuf m_plan, m_fol, m_chain, m_count, m_fix, m_badq, m_node;   // shared-node Merkle paths (dev.h mcse)
   DevBuf k_miss, k_missn;           // known openings: this workspace's miss list and its length
-  DevBuf t_cs, t_kis, t_gkind, t_gpar, t_ggrp, t_gwoff, t_w, t_gs, t_ge, t_lin, t_lout, t_loff, t_llen, t_tw, t_ops, t_vit, t_rin, t_rout, t_roff, t_rch, t_pbase, t_pw;
+  DevBuf t_cs, t_kis, t_gkind, t_gpar, t_ggrp, t_gwoff, t_w, t_gs, t_ge, t_lin, t_lout, t_loff, t_llen, t_tw, t_ops, t_vit, t_rin, t_rout, t_roff, t_rch, t_pbase, t_pw, t_gprog, t_gpoff;
   DevBuf j_blob, j_offs, j_skel, j_tok, j_ok;          // JSON / binary ingest, grown on demand
   DevBuf b_rsrc, b_rdst, b_rlen, b_coff, b_cval;       // the byte map
 };
@@ -311,6 +314,7 @@ void fill_scalars(const Circuit& C, DevCircuit& d) {
   d.noop_leaves = C.noop_leaves ? 1 : 0;
   d.n_gates = C.n_gate_eval; d.n_pp_terms = (int)C.n_pp_terms_per_round; d.n_lookup_terms = (int)C.n_lookup_terms_per_round;
   d.alpha_base_gates = C.alpha_base_gates;
+  d.prog_pih = -1;
   const Layout& L = C.L;
   d.pis = L.pis; d.wcap = L.wcap; d.zcap = L.zcap; d.qcap = L.qcap; d.o_const = L.o_const; d.o_sig = L.o_sig; d.o_wires = L.o_wires;
   d.o_zs = L.o_zs; d.o_pp = L.o_pp; d.o_quot = L.o_quot; d.o_lzs = L.o_lzs; d.o_zs_next = L.o_zs_next; d.o_lzs_next = L.o_lzs_next;
@@ -344,6 +348,7 @@ struct CircuitTables {
   std::vector<int32_t> gkind, ggrp, gwoff, gs, ge; std::vector<int64_t> gpar; std::vector<uint64_t> wts;
   std::vector<uint64_t> lin, lout; std::vector<int64_t> loff, llen;
   std::vector<uint32_t> rin, rout; std::vector<int64_t> roff; std::vector<int32_t> rch, pbase{0};
+  std::vector<uint64_t> gprog; std::vector<int64_t> gpoff;   // the lowered gate programs (circuit.hpp lower_gate_program)
 };
 CircuitTables circuit_tables(const Circuit& C) {
   CircuitTables t;
@@ -352,6 +357,12 @@ CircuitTables circuit_tables(const Circuit& C) {
     t.gkind.push_back(gd.kind); t.ggrp.push_back(C.sel_idx[g]);
     t.gpar.push_back(gd.p0); t.gpar.push_back(gd.p1); t.gpar.push_back(gd.p2);
     t.gwoff.push_back((int32_t)t.wts.size()); t.wts.insert(t.wts.end(), gd.weights.begin(), gd.weights.end());
+    t.gpoff.push_back(gd.kind == G_PROGRAM ? (int64_t)t.gprog.size() : -1);
+    if (gd.kind == G_PROGRAM) {
+      std::vector<uint64_t> low;
+      lower_gate_program(gd.prog, &low);
+      t.gprog.insert(t.gprog.end(), low.begin(), low.end());
+    }
   }
   t.gwoff.push_back((int32_t)t.wts.size());
   t.gs.assign(C.grp_start.begin(), C.grp_start.end()); t.ge.assign(C.grp_end.begin(), C.grp_end.end());
@@ -439,14 +450,21 @@ std::vector<int32_t> vanish_items(const Circuit& C, DevCircuit& d) {
       for (int64_t k = 0; k < parts; k++) item(VI_GATE, g, (int)k, p2v_coset_part_first_term(k));
     }
   d.vcls[2] = (int)(vit.size() / 4);
-  for (int g = 0; g < C.n_gate_eval; g++) if (kind(g) != G_POSEIDON && kind(g) != G_COSET) item(VI_GATE, g, 0, 0);
+  for (int g = 0; g < C.n_gate_eval; g++) if (kind(g) != G_POSEIDON && kind(g) != G_COSET && kind(g) != G_PROGRAM) item(VI_GATE, g, 0, 0);
   for (int j = 0; j < d.r; j++) item(VI_PP, j, 0, d.r + (int64_t)j * d.n_pp_terms);
   item(VI_ZS1, 0, 0, 0);
   d.vcls[3] = (int)(vit.size() / 4);
   if (d.nluts > 0)
     for (int j = 0; j < d.r; j++) item(VI_LOOKUP, j, 0, d.r + (int64_t)d.r * d.n_pp_terms + (int64_t)j * d.n_lookup_terms);
+  d.vcls[4] = (int)(vit.size() / 4);
+  {   // the program gates (vanish_prog.hip), one item each, the longest program first
+    std::vector<int> pg;
+    for (int g = 0; g < C.n_gate_eval; g++) if (kind(g) == G_PROGRAM) pg.push_back(g);
+    std::stable_sort(pg.begin(), pg.end(), [&](int x, int y) { return C.gates[x].prog.size() > C.gates[y].prog.size(); });
+    for (int g : pg) item(VI_GATE, g, 0, 0);
+  }
   d.n_vitems = (int)(vit.size() / 4);
-  d.vcls[4] = d.n_vitems;
+  d.vcls[5] = d.n_vitems;
   return vit;
 }
 }  // namespace
@@ -467,15 +485,73 @@ int p2v_circuit_from_json(const char* common_json, size_t common_len, const char
 
 int p2v_circuit_from_json_ex(const char* common_json, size_t common_len, const char* vkey_json, size_t vkey_len, uint32_t ext,
                              p2v_circuit** out) {
+  return p2v_circuit_from_json_gates(common_json, common_len, vkey_json, vkey_len, ext, nullptr, 0, out);
+}
+
+// the caller's gate programs, decoded (P2V_E_PARSE) after the checks that need no circuit:
+// P2V_E_ARG for a string registered twice or one that is a built-in gate's
+static int named_programs(const p2v_gate_program* progs, size_t nprogs, std::vector<NamedGateProgram>& out) {
+  if (nprogs && !progs) return fail(P2V_E_ARG, "null argument");
+  for (size_t i = 0; i < nprogs; i++) {
+    if (!progs[i].gate || (!progs[i].words && progs[i].nwords)) return fail(P2V_E_ARG, "null argument");
+    std::string name(progs[i].gate, progs[i].gate_len);
+    for (const auto& np : out) if (np.gate == name) return fail(P2V_E_ARG, "gate program registered twice: " + name);
+    if (parse_gate_string(name).kind != G_UNKNOWN) return fail(P2V_E_ARG, "a gate program cannot override a built-in gate: " + name);
+    out.push_back(NamedGateProgram{std::move(name), GateProgram{}});
+  }
+  return guarded(P2V_E_PARSE, [&] {
+    for (size_t i = 0; i < nprogs; i++) out[i].prog = decode_gate_program(progs[i].words, progs[i].nwords);
+  });
+}
+
+int p2v_circuit_from_json_gates(const char* common_json, size_t common_len, const char* vkey_json, size_t vkey_len, uint32_t ext,
+                                const p2v_gate_program* progs, size_t nprogs, p2v_circuit** out) {
   if (!common_json || !vkey_json || !out) return fail(P2V_E_ARG, "null argument");
   if (ext & ~P2V_EXT_PLONKY2) return fail(P2V_E_ARG, "unknown P2V_EXT_* flag");
+  std::vector<NamedGateProgram> np;
+  RCK(named_programs(progs, nprogs, np));
   return guarded(P2V_E_PARSE, [&] {
     JVal cj = parse_json(common_json, common_len);
     JVal vj = parse_json(vkey_json, vkey_len);
     auto pc = std::make_unique<p2v_circuit>();
-    pc->c = parse_circuit(cj, vj, ext);
+    pc->c = parse_circuit(cj, vj, ext, np);
     *out = pc.release();
   });
+}
+
+int p2v_circuit_num_program_gates(const p2v_circuit* pc) {
+  if (!pc) return fail(P2V_E_ARG, "null argument");
+  int k = 0;
+  for (int g = 0; g < pc->c.n_gate_eval; g++) k += pc->c.gates[g].kind == G_PROGRAM;
+  return k;
+}
+
+int p2v_gate_program_info(const uint64_t* words, size_t nwords, int64_t info[4]) {
+  if (!words || !info) return fail(P2V_E_ARG, "null argument");
+  return guarded(P2V_E_PARSE, [&] {
+    const GateProgram g = decode_gate_program(words, nwords);
+    info[0] = (int64_t)g.size(); info[1] = g.num_commits; info[2] = (int64_t)g.def.size();
+    info[3] = lower_gate_program(g, nullptr);
+  });
+}
+
+int p2v_gate_program_eval(const uint64_t* words, size_t nwords, const uint64_t* wires, int nwires, const uint64_t* consts, int nconsts,
+                          const uint64_t pih[4], uint64_t* out, int maxout) {
+  if (!words || nwires < 0 || nconsts < 0 || maxout < 0 || (nwires && !wires) || (nconsts && !consts) || (maxout && !out))
+    return fail(P2V_E_ARG, "null argument");
+  int n = 0;
+  const int rc = guarded(P2V_E_PARSE, [&] {
+    const GateProgram g = decode_gate_program(words, nwords);
+    if (g.max_wire >= nwires) throw CircuitError("(Array.!): gate program reads a wire beyond the row");
+    if (g.max_const >= nconsts) throw CircuitError("(Array.!): gate program reads a constant beyond the row");
+    if (g.max_pih >= 4) throw CircuitError("(!!): gate program reads a public-inputs-hash word beyond 4");
+    if (g.max_pih >= 0 && !pih) throw CircuitError("gate program reads the public-inputs hash, none given");
+    n = g.num_commits;
+    if (n <= maxout) eval_gate_program(g, wires, consts, pih, out);
+  });
+  if (rc != P2V_OK) return rc;
+  if (n > maxout) return fail(P2V_E_ARG, "p2v_gate_program_eval: more constraints than maxout");
+  return n;
 }
 
 int p2v_circuit_from_words(const uint64_t* words, size_t n, p2v_circuit** out) {
@@ -483,11 +559,18 @@ int p2v_circuit_from_words(const uint64_t* words, size_t n, p2v_circuit** out) {
 }
 
 int p2v_circuit_from_words_ex(const uint64_t* words, size_t n, uint32_t ext, p2v_circuit** out) {
+  return p2v_circuit_from_words_gates(words, n, ext, nullptr, 0, out);
+}
+
+int p2v_circuit_from_words_gates(const uint64_t* words, size_t n, uint32_t ext, const p2v_gate_program* progs, size_t nprogs,
+                                 p2v_circuit** out) {
   if (!words || !out) return fail(P2V_E_ARG, "null argument");
   if (ext & ~P2V_EXT_PLONKY2) return fail(P2V_E_ARG, "unknown P2V_EXT_* flag");
+  std::vector<NamedGateProgram> np;
+  RCK(named_programs(progs, nprogs, np));
   return guarded(P2V_E_PARSE, [&] {
     auto pc = std::make_unique<p2v_circuit>();
-    pc->c = parse_circuit_words(words, n, ext);
+    pc->c = parse_circuit_words(words, n, ext, np);
     *out = pc.release();
   });
 }
@@ -706,6 +789,7 @@ int p2v_verifier_create(const p2v_circuit* pc, int device, size_t max_batch, p2v
   ACK(upload(v->t_rin, t.rin, d.lut_rin)); ACK(upload(v->t_rout, t.rout, d.lut_rout)); ACK(upload(v->t_roff, t.roff, d.lut_roff));
   ACK(upload(v->t_rch, t.rch, d.lut_rchunks)); ACK(upload(v->t_pbase, t.pbase, d.lut_pbase));
   ACK(upload(v->t_pw, poseidon_part3_table(), d.pos_w));
+  ACK(upload(v->t_gprog, t.gprog, d.gprog)); ACK(upload(v->t_gpoff, t.gpoff, d.gate_poff));
   const size_t B = v->Bmax;
   const size_t chw = (size_t)(4 + 7 * d.r + 4 + 2 * d.S + 1 + d.Q + 4);
   v->in_bytes = (size_t)C.L.words * v->Bmax * 8;   // whole 64-proof tiles (P2V_FLAG_INPUT_TILED); allocated on first use
@@ -970,7 +1054,7 @@ int p2v_verifier_run_keyed(p2v_verifier* v, const uint64_t* proofs, const uint32
   if (d.n_lut_pieces > 0) k_lut<<<(d.r * d.n_lut_pieces * NPB + 3) / 4, 256, 0, sd>>>(d);
   DBG("k_lut", sd);
   T1(SLOT_LUT, sd);
-  // the vanishing items in three kernels (register allocation per class), timed together
+  // the vanishing items in one kernel per class (register allocation per class), timed together
   T0(SLOT_VANISH, sd);
   // (one wave per work-group; the _r2 forms hold exactly the standard 2 challenge rounds)
   const bool r2 = d.r == 2;
@@ -994,6 +1078,10 @@ int p2v_verifier_run_keyed(p2v_verifier* v, const uint64_t* proofs, const uint32
   }
   if (d.vcls[4] > d.vcls[3]) launch_vanish(r2 ? k_vanish_lookup_r2 : k_vanish_lookup_rn, d.vcls[3], d.vcls[4], NPB, sd, d);
   DBG("k_vanish_lookup", sd);
+  // the program gates (vanish_prog.hip): after the other classes on the side stream, so a circuit
+  // without them runs the launch sequence it always did
+  if (d.vcls[5] > d.vcls[4]) launch_vanish(r2 ? k_vanish_prog_r2 : k_vanish_prog_rn, d.vcls[4], d.vcls[5], NPB, sd, d);
+  DBG("k_vanish_prog", sd);
   T1(SLOT_VANISH, sd);
   T0(SLOT_VANISH_FINAL, sd);
   k_vanish_final<<<(d.B + 255) / 256, 256, 0, sd>>>(d);
@@ -1536,9 +1624,54 @@ static int selftest_field(int op, const uint64_t* a, const uint64_t* b, uint64_t
   return P2V_OK;
 }
 
+// p2v_selftest op 21: the gate-program interpreter (vanish_prog.hip) on items laid out as a proof's
+// openings are: b = nwires, nconsts, the program.  The program is checked here as at circuit
+// creation, so the kernel reads nothing outside an item and writes no slot past the file; like the
+// other ops' shared words, a b that does not pass is P2V_E_ARG, decided before any device call.
+static int selftest_prog(int device, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n) {
+  if (!b) return fail(P2V_E_ARG, "bad op / null argument");
+  if (b[0] > (1u << 20) || b[1] > (1u << 20)) return fail(P2V_E_ARG, "gate program rows beyond this build's limits");
+  if (n > (size_t)INT32_MAX - 64) return fail(P2V_E_ARG, "too many items");
+  const int64_t nw = (int64_t)b[0], nc = (int64_t)b[1];
+  GateProgram g;
+  std::vector<uint64_t> low;
+  try {
+    // the encoding's own instruction count bounds the walk: at most 3 words per instruction
+    if (b[2] != P2V_WORDS_GATE_MAGIC) throw ParseError("gate program: bad magic / version");
+    if (b[3] > (uint64_t)P2V_GATE_PROGRAM_MAX_INSTRS) throw CircuitError("gate program beyond this build's limits (instructions)");
+    g = decode_gate_program(b + 2, gate_program_extent(b + 2, 2 + 3 * (size_t)b[3]));
+    if (g.max_wire >= nw || g.max_const >= nc) throw CircuitError("(Array.!): gate program reads beyond the row");
+    if (g.max_pih >= 4) throw CircuitError("(!!): gate program reads a public-inputs-hash word beyond 4");
+    if (lower_gate_program(g, &low) > P2V_GATE_PROGRAM_MAX_LIVE) throw CircuitError("gate program beyond this build's limits (values alive at once)");
+  } catch (const std::exception& e) { return fail(P2V_E_ARG, std::string("selftest op 21: ") + e.what()); }
+  const int ndev = p2v_device_count();
+  if (ndev == 0) return fail(P2V_E_NODEVICE, "no HIP device");
+  if (device < 0 || device >= ndev) return fail(P2V_E_ARG, "bad device index");
+  if (n == 0 || g.num_commits == 0) return P2V_OK;
+  HCK(hipSetDevice(device));
+  const size_t w = (size_t)(2 * (nw + nc) + 4), wo = 2 * (size_t)g.num_commits;
+  DevCircuit d{};
+  d.prog_pih = 2 * (nw + nc);
+  d.o_wires = 0; d.o_const = 2 * nw;   // ngroups = nls = 0: Vars::k(i) is constant i
+  d.words = (int64_t)w; d.wstride = 1; d.tiled = 0;
+  d.n = (int32_t)n; d.B = (int32_t)((n + 63) / 64 * 64);
+  DevBuf da, dout, dprog;
+#define SCK(x) HCK_AS("p2v_selftest", x)
+  SCK(da.alloc(n * w * 8)); SCK(dout.alloc(n * wo * 8));
+  SCK(upload(dprog, low, d.gprog));
+  SCK(hipMemcpy(da.p, a, n * w * 8, hipMemcpyHostToDevice));
+  d.soa = (const uint64_t*)da.p;
+  hipLaunchKernelGGL(k_selftest_prog, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, 0, d, (uint64_t*)dout.p, g.num_commits);
+  SCK(hipGetLastError());
+  SCK(hipMemcpy(out, dout.p, n * wo * 8, hipMemcpyDeviceToHost));
+#undef SCK
+  return P2V_OK;
+}
+
 int p2v_selftest(int device, int op, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n) {
   const bool needs_b = op == 0 || op == 3 || op == 4 || op == 6;
-  if (op < 0 || op > 20 || (n && (!a || !out || (needs_b && !b)))) return fail(P2V_E_ARG, "bad op / null argument");
+  if (op < 0 || op > 21 || (n && (!a || !out || (needs_b && !b)))) return fail(P2V_E_ARG, "bad op / null argument");
+  if (op == 21) return selftest_prog(device, a, b, out, n);
   const int ndev = p2v_device_count();
   if (ndev == 0) return fail(P2V_E_NODEVICE, "no HIP device");
   if (device < 0 || device >= ndev) return fail(P2V_E_ARG, "bad device index");

@@ -82,6 +82,7 @@ GateDesc parse_gate_string(const std::string& s) {
   { Cur u{str}; if (u.open("ReducingGate") && u.kv_int("num_coeffs", &a)) { u.lit("<D=2>"); if (u.close()) { g.kind = G_REDUCING; g.p0 = a; return g; } } }
   { Cur u{str}; if (u.open("ReducingExtensionGate") && u.kv_int("num_coeffs", &a)) { u.lit("<D=2>"); if (u.close()) { g.kind = G_REDUCING_EXT; g.p0 = a; return g; } } }
   g.kind = G_UNKNOWN;
+  g.name = s;
   return g;
 }
 
@@ -114,6 +115,129 @@ static void gate_footprint(const GateDesc& g, int64_t& max_wire, int64_t& max_co
     case G_REDUCING_EXT: { int64_t n = g.p0; max_wire = std::max<int64_t>({5, 2 * n + 5, n >= 2 ? 4 * n + 3 : 5}); break; }
     default: break;
   }
+}
+
+// ------------------------------------------------------------------ gate programs
+// include/p2v.h "gate programs": the straight-line programs of Gate/Computation.hs:34-36 over
+// the Expr constructors of Algebra/Expr.hs:28-35, for gates outside the reference's list.
+static int gate_op_operands(uint64_t op) { return op == GP_ADD || op == GP_SUB || op == GP_MUL ? 2 : 1; }
+
+size_t gate_program_extent(const uint64_t* w, size_t max_words) {
+  if (max_words < 2 || w[0] != P2V_WORDS_GATE_MAGIC) throw ParseError("gate program: bad magic / version");
+  if (w[1] > (uint64_t)max_words) throw ParseError("gate program: truncated");
+  size_t i = 2;
+  for (uint64_t k = 0; k < w[1]; k++) {
+    if (i >= max_words) throw ParseError("gate program: truncated");
+    if (w[i] >= GP_NUM_OPS) throw ParseError("gate program: unknown opcode " + std::to_string(w[i]));
+    i += 1 + (size_t)gate_op_operands(w[i]);
+    if (i > max_words) throw ParseError("gate program: truncated");
+  }
+  return i;
+}
+
+GateProgram decode_gate_program(const uint64_t* w, size_t n) {
+  if (gate_program_extent(w, n) != n) throw ParseError("gate program: trailing words");
+  GateProgram g;
+  const size_t ni = (size_t)w[1];
+  g.op.reserve(ni); g.a.reserve(ni); g.b.reserve(ni);
+  size_t i = 2;
+  for (size_t k = 0; k < ni; k++) {
+    const uint8_t op = (uint8_t)w[i];
+    uint64_t a = w[i + 1], b = op == GP_ADD || op == GP_SUB || op == GP_MUL ? w[i + 2] : 0;
+    i += 1 + (size_t)gate_op_operands(op);
+    const uint64_t nvals = g.def.size();
+    switch (op) {
+      case GP_WIRE: g.max_wire = std::max<int64_t>(g.max_wire, (int64_t)std::min<uint64_t>(a, INT64_MAX)); break;
+      case GP_CONST: g.max_const = std::max<int64_t>(g.max_const, (int64_t)std::min<uint64_t>(a, INT64_MAX)); break;
+      case GP_PIHASH: g.max_pih = std::max<int64_t>(g.max_pih, (int64_t)std::min<uint64_t>(a, INT64_MAX)); break;
+      case GP_LIT: a %= gl::P; break;
+      default:
+        if (a >= nvals || (gate_op_operands(op) == 2 && b >= nvals))
+          throw ParseError("gate program: instruction " + std::to_string(k) + " reads a value that is not an earlier one");
+    }
+    if (op == GP_COMMIT) g.num_commits++;
+    else g.def.push_back((int32_t)k);
+    g.op.push_back(op); g.a.push_back(a); g.b.push_back(b);
+  }
+  return g;
+}
+
+void eval_gate_program(const GateProgram& g, const uint64_t* wires, const uint64_t* consts, const uint64_t* pih, uint64_t* out) {
+  std::vector<gl::E> v;
+  v.reserve(g.def.size());
+  for (size_t k = 0; k < g.size(); k++) {
+    const uint64_t a = g.a[k], b = g.b[k];
+    switch (g.op[k]) {
+      case GP_WIRE: v.push_back(gl::E{wires[2 * a] % gl::P, wires[2 * a + 1] % gl::P}); break;
+      case GP_CONST: v.push_back(gl::E{consts[2 * a] % gl::P, consts[2 * a + 1] % gl::P}); break;
+      case GP_PIHASH: v.push_back(gl::eb(pih[a] % gl::P)); break;
+      case GP_LIT: v.push_back(gl::eb(a)); break;
+      case GP_ADD: v.push_back(gl::eadd(v[a], v[b])); break;
+      case GP_SUB: v.push_back(gl::esub(v[a], v[b])); break;
+      case GP_MUL: v.push_back(gl::emul(v[a], v[b])); break;
+      case GP_IMG: v.push_back(gl::E{gl::mul_small(v[a].b, 7), v[a].a}); break;   // (0, 1) * x, X^2 = 7
+      default: *out++ = v[a].a; *out++ = v[a].b; break;                           // GP_COMMIT
+    }
+  }
+}
+
+int lower_gate_program(const GateProgram& g, std::vector<uint64_t>* out) {
+  const size_t nv = g.def.size();
+  auto leaf = [&](uint64_t val) { return g.op[g.def[val]] <= GP_LIT; };
+  // last use of every value (the instruction index; its own when nothing reads it)
+  std::vector<int32_t> last(nv);
+  for (size_t v = 0; v < nv; v++) last[v] = g.def[v];
+  for (size_t k = 0; k < g.size(); k++) {
+    if (g.op[k] <= GP_LIT) continue;
+    last[g.a[k]] = (int32_t)k;
+    if (gate_op_operands(g.op[k]) == 2) last[g.b[k]] = (int32_t)k;
+  }
+  std::vector<int32_t> slot(nv, -1);
+  std::vector<char> used;   // slot -> occupied
+  int nslots = 0;
+  if (out) { out->clear(); out->push_back(0); }
+  uint64_t emitted = 0;
+  size_t val = 0;
+  for (size_t k = 0; k < g.size(); k++) {
+    const uint8_t op = g.op[k];
+    if (op <= GP_LIT) { val++; continue; }
+    const int nops = gate_op_operands(op);
+    uint64_t w[3] = {op, 0, 0};
+    for (int j = 0; j < nops; j++) {
+      const uint64_t x = j ? g.b[k] : g.a[k];
+      uint64_t kind, arg;
+      if (leaf(x)) { kind = GPK_WIRE + g.op[g.def[x]]; arg = g.a[g.def[x]]; }
+      else { kind = GPK_SLOT; arg = (uint64_t)slot[x]; }
+      w[0] |= kind << (16 + 8 * j);
+      w[1 + j] = arg;
+    }
+    // the operands are read before the result is written: a value whose last use this is frees its slot first
+    for (int j = 0; j < nops; j++) {
+      const uint64_t x = j ? g.b[k] : g.a[k];
+      if (!leaf(x) && last[x] == (int32_t)k && slot[x] >= 0 && used[slot[x]]) used[slot[x]] = 0;
+    }
+    if (op != GP_COMMIT) {
+      int s = 0;
+      while (s < (int)used.size() && used[s]) s++;
+      if (s == (int)used.size()) used.push_back(0);
+      used[s] = 1;
+      slot[val] = s;
+      nslots = std::max(nslots, s + 1);
+      w[0] |= (uint64_t)s << 8;
+      if (last[val] == (int32_t)k) used[s] = 0;   // never read: the slot is free again at once
+      val++;
+    }
+    if (out) out->insert(out->end(), w, w + 3);
+    emitted++;
+  }
+  if (out) (*out)[0] = emitted;
+  return nslots;
+}
+
+// An UnknownGate with a registered program becomes a G_PROGRAM gate
+static void attach_program(GateDesc& g, const std::vector<NamedGateProgram>& progs) {
+  if (g.kind != G_UNKNOWN) return;
+  for (const auto& np : progs) if (np.gate == g.name) { g.kind = G_PROGRAM; g.prog = np.prog; return; }
 }
 
 static void digest_of(const JVal& d, uint64_t* out) {   // Hash/Digest.hs:40-44
@@ -165,7 +289,7 @@ static void fri_steps(Circuit& C, int tag, const std::vector<int64_t>& a) {
 
 static void finalize_circuit(Circuit& C);
 
-Circuit parse_circuit(const JVal& common, const JVal& vkey, uint32_t ext) {
+Circuit parse_circuit(const JVal& common, const JVal& vkey, uint32_t ext, const std::vector<NamedGateProgram>& progs) {
   Circuit C;
   C.ext = ext;
   const JVal& cfg = common.at("config");
@@ -211,6 +335,7 @@ Circuit parse_circuit(const JVal& common, const JVal& vkey, uint32_t ext) {
   for (const auto& g : common.at("gates").arr()) {
     if (g.kind != JVal::Str) throw ParseError("gate must be a string");
     C.gates.push_back(parse_gate_string(g.text));
+    attach_program(C.gates.back(), progs);
   }
   const JVal& si = common.at("selectors_info");
   for (const auto& x : si.at("selector_indices").arr()) C.sel_idx.push_back(j_i32(x));
@@ -280,6 +405,14 @@ static void finalize_circuit(Circuit& C) {
     if (grp < 0 || grp >= ngroups) throw CircuitError("selector_groups !! group_idx: index out of range");
     int64_t mw, mc;
     gate_footprint(gd, mw, mc);
+    if (gd.kind == G_PROGRAM) {   // the program's own footprint and this build's limits (include/p2v.h)
+      mw = gd.prog.max_wire; mc = gd.prog.max_const;
+      if (gd.prog.max_pih >= 4) throw CircuitError("(!!): gate program reads a public-inputs-hash word beyond 4: " + gd.text);
+      if (gd.prog.size() > (size_t)P2V_GATE_PROGRAM_MAX_INSTRS)
+        throw CircuitError("gate program beyond this build's limits (instructions, DESIGN.md §8): " + gd.text);
+      if (lower_gate_program(gd.prog, nullptr) > P2V_GATE_PROGRAM_MAX_LIVE)
+        throw CircuitError("gate program beyond this build's limits (values alive at once, DESIGN.md §8): " + gd.text);
+    }
     if (mw >= C.num_wires) throw CircuitError("(Array.!): gate reads a wire beyond num_wires: " + gd.text);
     if (mc >= C.num_gate_consts) throw CircuitError("(Array.!): gate reads a constant beyond num_constants: " + gd.text);
   }
@@ -509,7 +642,7 @@ const char* gate_name(int k) {
 }
 }  // namespace
 
-Circuit parse_circuit_words(const uint64_t* w, size_t n, uint32_t ext) {
+Circuit parse_circuit_words(const uint64_t* w, size_t n, uint32_t ext, const std::vector<NamedGateProgram>& progs) {
   WordReader R{w, n};
   R.magic(P2V_WORDS_CIRCUIT_MAGIC);
   Circuit C;
@@ -563,11 +696,13 @@ Circuit parse_circuit_words(const uint64_t* w, size_t n, uint32_t ext) {
         std::string name;
         for (int64_t m = R.len("UnknownGate name"); m > 0; m--) name.push_back((char)R.u("name byte"));
         params = name;
+        g.name = name;
         break; }
       default: throw ParseError("words: unknown Gate constructor tag " + std::to_string(t));
     }
     g.kind = (int32_t)t;
     g.text = std::string(gate_name((int)t)) + "(" + params + ")";
+    attach_program(g, progs);
     C.gates.push_back(std::move(g));
   }
   // SelectorsInfo (Types.hs:90-95)

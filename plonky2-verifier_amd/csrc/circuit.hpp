@@ -12,14 +12,45 @@ namespace p2v {
 
 enum GateKind : int32_t {   // Gate/Base.hs:27-45
   G_ARITH = 0, G_ARITH_EXT, G_BASESUM, G_COSET, G_CONST, G_EXP, G_LOOKUP, G_LOOKUPTABLE,
-  G_MULEXT, G_NOOP, G_PI, G_POSEIDON, G_POSEIDON_MDS, G_RANDACC, G_REDUCING, G_REDUCING_EXT, G_UNKNOWN
+  G_MULEXT, G_NOOP, G_PI, G_POSEIDON, G_POSEIDON_MDS, G_RANDACC, G_REDUCING, G_REDUCING_EXT, G_UNKNOWN,
+  G_PROGRAM   // an UnknownGate whose constraints are a caller's program (include/p2v.h "gate programs")
 };
+
+// A gate program (include/p2v.h, version-1 encoding), decoded and checked for form: SSA,
+// straight-line, every operand an earlier value.  Instruction i is op[i] with operands a[i], b[i]
+// (value numbers; for the leaf ops a[i] is the index / the literal reduced mod p).
+enum GateOp : uint8_t { GP_WIRE = 0, GP_CONST, GP_PIHASH, GP_LIT, GP_ADD, GP_SUB, GP_MUL, GP_IMG, GP_COMMIT, GP_NUM_OPS };
+struct GateProgram {
+  std::vector<uint8_t> op;
+  std::vector<uint64_t> a, b;
+  std::vector<int32_t> def;        // value number -> the instruction that defines it
+  int num_commits = 0;
+  int64_t max_wire = -1, max_const = -1, max_pih = -1;
+  size_t size() const { return op.size(); }
+  bool empty() const { return op.empty(); }
+};
+// throws ParseError (bad magic, truncation, trailing words, unknown opcode, operand not an earlier value)
+GateProgram decode_gate_program(const uint64_t* words, size_t n);
+// the number of words of the encoding that starts at `words` (walks at most max_words; ParseError)
+size_t gate_program_extent(const uint64_t* words, size_t max_words);
+// F^2 rows in, constraints (re, im) out; the caller has checked the indices against the rows
+void eval_gate_program(const GateProgram& g, const uint64_t* wires, const uint64_t* consts, const uint64_t* pih, uint64_t* out);
+// What the device interpreter reads (vanish_prog.hip): [count, then 3 words per instruction
+// {op | slot << 8 | kind_a << 16 | kind_b << 24, a, b}].  The leaf values are operand kinds of
+// their own; every other value gets an LDS slot by liveness (alive from its instruction to its
+// last use): straight-line SSA lifetimes are intervals, so taking the lowest free slot in
+// program order uses exactly as many slots as values are alive at once.  Returns that number.
+enum { GPK_SLOT = 0, GPK_WIRE, GPK_CONST, GPK_PIHASH, GPK_LIT };
+int lower_gate_program(const GateProgram& g, std::vector<uint64_t>* out);
+struct NamedGateProgram { std::string gate; GateProgram prog; };
 
 struct GateDesc {
   int32_t kind = G_UNKNOWN;
   int64_t p0 = 0, p1 = 0, p2 = 0;
   std::vector<uint64_t> weights;   // CosetInterpolationGate barycentric weights
   std::string text;
+  std::string name;                // UnknownGate: the gate string as given (what a gate program is matched by)
+  GateProgram prog;                // G_PROGRAM
 };
 
 // Fixed per-circuit packed proof layout (u64 words).  Order:
@@ -79,9 +110,12 @@ struct Circuit {
   int64_t trace_words = 0;
 };
 
-Circuit parse_circuit(const JVal& common, const JVal& vkey, uint32_t ext = 0);   // throws ParseError / CircuitError
+// progs: gate programs by gate string; an UnknownGate with one becomes a G_PROGRAM gate
+Circuit parse_circuit(const JVal& common, const JVal& vkey, uint32_t ext = 0,
+                      const std::vector<NamedGateProgram>& progs = {});   // throws ParseError / CircuitError
 // the same from the word-encoded Types.hs values (include/p2v.h, "Word-encoded values")
-Circuit parse_circuit_words(const uint64_t* words, size_t n, uint32_t ext = 0);   // throws ParseError / CircuitError
+Circuit parse_circuit_words(const uint64_t* words, size_t n, uint32_t ext = 0,
+                            const std::vector<NamedGateProgram>& progs = {});   // throws ParseError / CircuitError
 void pack_proof_words(const Circuit& c, const uint64_t* words, size_t n, uint64_t* dst);   // ParseError / ShapeError
 // a VerifierOnlyCircuitData JSON in the key encoding (c.key_words() words: the cap digests, then
 // circuit_digest); ParseError, or CircuitError when the cap is not of the circuit's length

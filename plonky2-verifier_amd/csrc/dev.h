@@ -79,7 +79,7 @@ struct DevCircuit {
   int32_t ntops;
   const int32_t* vitems;           // vanishing work items [n_vitems][4] = {VI_*, a, b, first term}
   int32_t n_vitems;
-  int32_t vcls[5];                 // item ranges of the vanishing kernel classes (Poseidon, coset, misc, lookup)
+  int32_t vcls[6];                 // item ranges of the vanishing kernel classes (Poseidon, coset, misc, lookup, program)
   const uint64_t* pos_w;           // PoseidonGate part 3: W = A'M [12][12] then k = A' rc [12] (vanish_poseidon.hip)
   // batch buffers
   const uint64_t* soa;             // the caller's batch, read in place: [n][words], or 64-proof tiles (devcommon.h ld())
@@ -115,7 +115,14 @@ struct DevCircuit {
   unsigned long long* kstat;       // per circuit and device: hits, misses, rows inserted
   uint32_t* kmiss;                 // [Q][B] of this workspace: the run's missed openings q << 22 | p
   int32_t* kmissn;                 // entries of kmiss (k_status zeroes it for the next run)
+  // Gate programs (include/p2v.h "gate programs", vanish_prog.hip): the lowered programs of the
+  // circuit's G_PROGRAM gates, concatenated; gate g's starts at gprog[gate_poff[g]] (-1: none) with
+  // its instruction count, then 3 words per instruction (circuit.hpp lower_gate_program)
+  const uint64_t* gprog;
+  const int64_t* gate_poff;        // [n_gates]
+  int64_t prog_pih;                // p2v_selftest op 21: the item word of the hash words; -1: the challenge buffer
 };
+#define P2V_PROG_SLOTS 32          // LDS slots of the interpreter = P2V_GATE_PROGRAM_MAX_LIVE (include/p2v.h)
 #define P2V_KNOWN_EMPTY 0u
 #define P2V_KNOWN_VALID 1u
 #define P2V_KNOWN_BUSY 2u          // claimed by the one lane group that writes the row

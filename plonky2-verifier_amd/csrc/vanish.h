@@ -201,10 +201,16 @@ __device__ __forceinline__ void gate_random_access(const Vars& V, A_& A, int nbi
 // VK_POSEIDON: PoseidonGate parts; VK_COSET: CosetInterpolationGate; VK_MISC: everything else.
 // VK_LOOKUP: the lookup-argument items (Plonk/Lookups.hs:45-132), a class of their own so that
 // their register demand does not set the misc kernel's.
-enum { VK_POSEIDON = 0, VK_COSET = 1, VK_MISC = 2, VK_LOOKUP = 3 };
+// VK_PROG: the gates whose constraints are a caller's program (include/p2v.h "gate programs"),
+// interpreted by vanish_prog.hip, the only translation unit that instantiates this class.
+enum { VK_POSEIDON = 0, VK_COSET = 1, VK_MISC = 2, VK_LOOKUP = 3, VK_PROG = 4 };
+
+template <int R>
+__device__ void gate_program(const DevCircuit& c, const Vars& V, Acc<R>& A, int g);
 
 template <int CLS, class A_>
 __device__ __forceinline__ void eval_gate(const DevCircuit& c, const Vars& V, A_& A, int g, int part) {
+  if constexpr (CLS == VK_PROG) { (void)part; gate_program(c, V, A, g); return; }
   const int64_t p0 = c.gate_par[3 * g], p1 = c.gate_par[3 * g + 1], p2 = c.gate_par[3 * g + 2];
   if constexpr (CLS == VK_POSEIDON) { (void)p0; (void)p1; (void)p2; gate_poseidon(V, A, part); return; }
   if constexpr (CLS == VK_COSET) { gate_coset(c, V, A, (int)p0, p1, c.weights + c.gate_woff[g], c.gate_woff[g + 1] - c.gate_woff[g], part); return; }

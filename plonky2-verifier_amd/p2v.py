@@ -99,6 +99,10 @@ class _Info(ctypes.Structure):
     ]
 
 
+class _GateProgramC(ctypes.Structure):   # p2v_gate_program
+    _fields_ = [("gate", ctypes.c_char_p), ("gate_len", ctypes.c_size_t), ("words", ctypes.c_void_p), ("nwords", ctypes.c_size_t)]
+
+
 _lib = None
 
 
@@ -152,6 +156,12 @@ def lib() -> ctypes.CDLL:
     L.p2v_circuit_known_stats.argtypes = [vp, ctypes.c_int, u64p]
     L.p2v_verifier_run_keyed.argtypes = [vp, u64p, vp, sz, i8p, u64p, vp, ctypes.c_uint32]
     L.p2v_verify_batch_keyed.argtypes = [vp, u64p, vp, sz, i8p, ctypes.c_int]
+    L.p2v_circuit_from_json_gates.argtypes = [ctypes.c_char_p, sz, ctypes.c_char_p, sz, ctypes.c_uint32,
+                                              ctypes.POINTER(_GateProgramC), sz, ctypes.POINTER(vp)]
+    L.p2v_circuit_from_words_gates.argtypes = [u64p, sz, ctypes.c_uint32, ctypes.POINTER(_GateProgramC), sz, ctypes.POINTER(vp)]
+    L.p2v_circuit_num_program_gates.argtypes = [vp]
+    L.p2v_gate_program_eval.argtypes = [u64p, sz, u64p, ctypes.c_int, u64p, ctypes.c_int, u64p, u64p, ctypes.c_int]
+    L.p2v_gate_program_info.argtypes = [u64p, sz, ctypes.POINTER(ctypes.c_int64)]
     L.p2v_kernel_names.restype = ctypes.c_char_p
     L.p2v_last_error_message.restype = ctypes.c_char_p
     L.p2v_version.restype = ctypes.c_char_p
@@ -187,6 +197,143 @@ def _check(rc: int) -> None:
 
 def _bytes(x: Union[str, bytes]) -> bytes:
     return x.encode() if isinstance(x, str) else bytes(x)
+
+
+class GateExpr:
+    """A value of a GateProgram under construction: F^2 arithmetic by + - * and .img()."""
+    __slots__ = ("prog", "idx")
+
+    def __init__(self, prog: "GateProgram", idx: int):
+        self.prog, self.idx = prog, idx
+
+    def _other(self, o) -> "GateExpr":
+        if isinstance(o, GateExpr):
+            if o.prog is not self.prog:
+                raise ValueError("values of two different gate programs")
+            return o
+        return self.prog.lit(int(o))
+
+    def __add__(self, o):
+        return self.prog._emit(4, self.idx, self._other(o).idx)
+
+    def __radd__(self, o):
+        return self.prog._emit(4, self._other(o).idx, self.idx)
+
+    def __sub__(self, o):
+        return self.prog._emit(5, self.idx, self._other(o).idx)
+
+    def __rsub__(self, o):
+        return self.prog._emit(5, self._other(o).idx, self.idx)
+
+    def __mul__(self, o):
+        return self.prog._emit(6, self.idx, self._other(o).idx)
+
+    def __rmul__(self, o):
+        return self.prog._emit(6, self._other(o).idx, self.idx)
+
+    def img(self) -> "GateExpr":
+        """(0, 1) * self (ImgE, Algebra/Expr.hs:138)."""
+        return self.prog._emit(7, self.idx)
+
+
+class GateProgram:
+    """Builder of a gate's constraint program (include/p2v.h "gate programs"): the straight-line
+    programs of the reference's own gates (Gate/Computation.hs) for a gate string it does not know.
+
+        g = GateProgram()
+        g.commit(g.wire(3) - g.const(0) * g.wire(0) * g.wire(1) - g.const(1) * g.wire(2))
+        vk = VerifierCircuitData.from_json(common, vkey, gates={"MyGate { .. }": g})
+
+    Leaf values (wire, const, pi_hash, lit) are memoised, so naming one twice costs nothing."""
+
+    OPS = ("WIRE", "CONST", "PIHASH", "LIT", "ADD", "SUB", "MUL", "IMG", "COMMIT")
+
+    def __init__(self):
+        self.instrs: List[tuple] = []   # (op, operands...)
+        self.num_values = 0
+        self.num_commits = 0
+        self._leaf = {}
+
+    def _emit(self, op: int, *args: int) -> GateExpr:
+        self.instrs.append((op,) + tuple(args))
+        self.num_values += 1
+        return GateExpr(self, self.num_values - 1)
+
+    def _leaf_value(self, op: int, k: int) -> GateExpr:
+        if (op, k) not in self._leaf:
+            self._leaf[(op, k)] = self._emit(op, k)
+        return self._leaf[(op, k)]
+
+    def wire(self, k: int) -> GateExpr:
+        return self._leaf_value(0, int(k))
+
+    def const(self, k: int) -> GateExpr:
+        return self._leaf_value(1, int(k))
+
+    def pi_hash(self, k: int) -> GateExpr:
+        return self._leaf_value(2, int(k))
+
+    def lit(self, x: int) -> GateExpr:
+        return self._leaf_value(3, int(x) % P)
+
+    def commit(self, e) -> None:
+        e = e if isinstance(e, GateExpr) else self.lit(int(e))
+        if e.prog is not self:
+            raise ValueError("a value of another gate program")
+        self.instrs.append((8, e.idx))
+        self.num_commits += 1
+
+    def commit_ext(self, pair) -> None:
+        """commitExt (Gate/Computation.hs:75-76): the two coordinates of a simulated extension value."""
+        u, v = pair
+        self.commit(u)
+        self.commit(v)
+
+    def words(self) -> np.ndarray:
+        w = [WORDS_GATE_MAGIC, len(self.instrs)]
+        for ins in self.instrs:
+            w.extend(ins)
+        return np.array([x & _M64 for x in w], dtype=np.uint64)
+
+    def evaluate(self, wires, consts, pih) -> np.ndarray:
+        """The constraints [num_commits, 2] of the rows `wires` [nw, 2], `consts` [nc, 2] (F^2) and
+        `pih` [4], through the host evaluator p2v_gate_program_eval."""
+        return gate_program_eval(self.words(), wires, consts, pih)
+
+
+def gate_program_eval(words: np.ndarray, wires, consts, pih, maxout: int = 1 << 16) -> np.ndarray:
+    w = np.ascontiguousarray(words, dtype=np.uint64)
+    wr = np.ascontiguousarray(wires, dtype=np.uint64).reshape(-1, 2)
+    cs = np.ascontiguousarray(consts, dtype=np.uint64).reshape(-1, 2)
+    ph = np.ascontiguousarray(pih, dtype=np.uint64).reshape(4)
+    out = np.zeros((maxout, 2), dtype=np.uint64)
+    n = lib().p2v_gate_program_eval(w.ctypes.data, w.size, wr.ctypes.data, wr.shape[0], cs.ctypes.data, cs.shape[0],
+                                    ph.ctypes.data, out.ctypes.data, maxout)
+    if n < 0:
+        _check(n)
+    return out[:n].copy()
+
+
+def gate_program_info(words: np.ndarray) -> dict:
+    """p2v_gate_program_info: the library's reading of an encoding (P2VError if malformed):
+    instructions, commits, values, and `slots`, the results alive at once = the LDS slots the
+    device interpreter's lowering assigns (at most GATE_PROGRAM_MAX_LIVE in a circuit)."""
+    w = np.ascontiguousarray(words, dtype=np.uint64)
+    info = (ctypes.c_int64 * 4)()
+    _check(lib().p2v_gate_program_info(w.ctypes.data, w.size, info))
+    return {"instructions": info[0], "commits": info[1], "values": info[2], "slots": info[3]}
+
+
+def _gate_programs(gates: dict):
+    """{gate string: GateProgram | words} -> (p2v_gate_program array, the objects it points into)."""
+    keep = []
+    for name, g in gates.items():
+        w = g.words() if isinstance(g, GateProgram) else np.ascontiguousarray(g, dtype=np.uint64)
+        keep.append((_bytes(name), w))
+    arr = (_GateProgramC * max(1, len(keep)))()
+    for i, (nm, w) in enumerate(keep):
+        arr[i] = _GateProgramC(nm, len(nm), w.ctypes.data, w.size)
+    return arr, keep
 
 
 @dataclass(frozen=True)
@@ -228,21 +375,40 @@ class VerifierCircuitData:
             tuple(inf.leaf_widths), inf.ext)
 
     @classmethod
-    def from_json(cls, common_json: Union[str, bytes], vkey_json: Union[str, bytes], ext: int = 0) -> "VerifierCircuitData":
+    def from_json(cls, common_json: Union[str, bytes], vkey_json: Union[str, bytes], ext: int = 0,
+                  gates: Optional[dict] = None) -> "VerifierCircuitData":
         """ext: opt-in plonky2 conventions the reference lacks (EXT_* below, include/p2v.h);
-        0 = exactly the reference's semantics."""
+        0 = exactly the reference's semantics.  gates: {gate string: GateProgram (or its words)}
+        for gates outside the reference's list (p2v_circuit_from_json_gates); None: none."""
         c, v = _bytes(common_json), _bytes(vkey_json)
         h = ctypes.c_void_p()
-        _check(lib().p2v_circuit_from_json_ex(c, len(c), v, len(v), ext, ctypes.byref(h)))
+        if gates is None:
+            _check(lib().p2v_circuit_from_json_ex(c, len(c), v, len(v), ext, ctypes.byref(h)))
+        else:
+            arr, keep = _gate_programs(gates)
+            _check(lib().p2v_circuit_from_json_gates(c, len(c), v, len(v), ext, arr, len(keep), ctypes.byref(h)))
         return cls(h.value)
 
     @classmethod
-    def from_words(cls, words: np.ndarray, ext: int = 0) -> "VerifierCircuitData":
-        """The word-encoded Types.hs value (include/p2v.h; what the Haskell shim marshals)."""
+    def from_words(cls, words: np.ndarray, ext: int = 0, gates: Optional[dict] = None) -> "VerifierCircuitData":
+        """The word-encoded Types.hs value (include/p2v.h; what the Haskell shim marshals);
+        gates as in from_json, matched by the UnknownGate's name."""
         w = np.ascontiguousarray(words, dtype=np.uint64)
         h = ctypes.c_void_p()
-        _check(lib().p2v_circuit_from_words_ex(w.ctypes.data, w.size, ext, ctypes.byref(h)))
+        if gates is None:
+            _check(lib().p2v_circuit_from_words_ex(w.ctypes.data, w.size, ext, ctypes.byref(h)))
+        else:
+            arr, keep = _gate_programs(gates)
+            _check(lib().p2v_circuit_from_words_gates(w.ctypes.data, w.size, ext, arr, len(keep), ctypes.byref(h)))
         return cls(h.value)
+
+    @property
+    def num_program_gates(self) -> int:
+        """Gates of the circuit evaluated by a registered program (p2v_circuit_num_program_gates)."""
+        n = lib().p2v_circuit_num_program_gates(self._h)
+        if n < 0:
+            _check(n)
+        return n
 
     @property
     def handle(self) -> ctypes.c_void_p:
@@ -664,9 +830,23 @@ def device_selftest(op: int, a: np.ndarray, b: Optional[np.ndarray] = None, devi
     8..11 taken as 0, words 0..3 returned), one MDS layer (op 4), the S-box forms (ops 5-8, x^7;
     op 6 the grouped pair (a[i], b[i]) -> out [n, 2]) and the latency forms of the permutation
     (ops 9-11: row, quad, pair) on `device`.  Ops 12-20: the F / F^2 arithmetic and the FRI query
-    code (a = [n, item words], b = the op's shared words, out = [n, result words]; see p2v.h)."""
+    code (a = [n, item words], b = the op's shared words, out = [n, result words]; see p2v.h).
+    Op 21: the gate-program interpreter, b = [nwires, nconsts] + GateProgram.words()."""
     a = np.ascontiguousarray(a, dtype=np.uint64)
     n = a.shape[0]
+    if op == 21:   # b = [nwires, nconsts, program words]; out: 2 words per COMMIT of the program
+        bb = np.ascontiguousarray(b, dtype=np.uint64).reshape(-1)
+        if bb.size < 4:
+            raise ValueError("selftest op 21: b = [nwires, nconsts] + program words")
+        # p2v_selftest has no length for b and reads the encoding as far as its instruction count
+        # says; the library's own decoder, given the length, says first that the words end there
+        ncommit = gate_program_info(bb[2:])["commits"]
+        win = 2 * (int(bb[0]) + int(bb[1])) + 4
+        if a.size != n * win:
+            raise ValueError(f"selftest op 21: items of {win} words expected, got shape {a.shape}")
+        out = np.zeros((n, 2 * ncommit), dtype=np.uint64)
+        _check(lib().p2v_selftest(device, op, a.ctypes.data, bb.ctypes.data, out.ctypes.data, n))
+        return out
     if 12 <= op <= 20:
         win = {12: 2, 13: 4, 14: 1, 15: 2, 16: 4, 17: 1, 18: 2}.get(op)
         if win is None:
@@ -880,6 +1060,8 @@ def verify_sharded(vkey: VerifierCircuitData, packed: np.ndarray, rank: int, wor
 P = 0xFFFFFFFF00000001   # Goldilocks modulus (Algebra/Goldilocks.hs)
 WORDS_CIRCUIT_MAGIC = 0x5032564300000001
 WORDS_PROOF_MAGIC = 0x5032565000000001
+WORDS_GATE_MAGIC = 0x5032564700000001    # "P2VG", version 1 (gate programs)
+GATE_PROGRAM_MAX_INSTRS, GATE_PROGRAM_MAX_LIVE = 16384, 32   # include/p2v.h
 _M64 = (1 << 64) - 1
 
 _GATE_RE = [   # (tag, regex) in Gate/Parser.hs order of alternatives; groups = Int fields
