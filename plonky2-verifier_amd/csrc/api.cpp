@@ -133,7 +133,7 @@ struct Event : Owned<hipEvent_t, hipEventDestroy> {
 }  // namespace
 
 struct HostPipe;
-// The circuit's known openings of tree 0 on one device (kernels.hip k_merkle_known): the rows, their
+// The circuit's known openings of tree 0 on one device (merkle.hip k_merkle_known): the rows, their
 // flags and the three counters.  Shared by every workspace of the circuit on that device; it warms
 // across runs and never affects a result, only time.
 struct KnownTable {
@@ -967,7 +967,7 @@ int p2v_verifier_run_keyed(p2v_verifier* v, const uint64_t* proofs, const uint32
   else if (v->transcript_mode == 3) tl = 1;
   else if (v->transcript_mode == 4) tl = 2;
   const int nt_blocks = (tl * d.B + 255) / 256;
-  // Known openings of tree 0 (kernels.hip k_merkle_known): unkeyed runs above the latency mode with
+  // Known openings of tree 0 (merkle.hip k_merkle_known): unkeyed runs above the latency mode with
   // the shared-node paths.  Tree 0 then leaves the leaf units and the plan / chains / resolve; its
   // statuses come from the probe and the miss kernel at the head of the side stream.
   const bool lat = d.n <= v->lat_max_batch;
@@ -1098,7 +1098,7 @@ int p2v_verifier_run_keyed(p2v_verifier* v, const uint64_t* proofs, const uint32
   const int merkle_units = d.Q * d.T * NPB;
   if (lat) k_merkle_row<<<(unsigned)(((int64_t)d.Q * d.T * d.n * 16 + 255) / 256), 256, 0, st>>>(d);
   else if (d.mcse) {
-    // shared nodes once: plan + bucketed chains + followers' statuses (kernels.hip); the chain
+    // shared nodes once: plan + bucketed chains + followers' statuses (merkle.hip); the chain
     // grid covers every bucket's last partial wave
     const int ncls = 1 + d.S;
     // k_merkle_resolve zeroes the bucket counters for the next run; a run that stopped between

@@ -8,7 +8,7 @@
 #define P2V_MAX_R 4
 #define P2V_LUT_CHUNK 16   // baby steps of the LUT evaluation
 #define P2V_LUT_PIECE 256  // chunks per k_lut work unit (4096 table entries)
-// launch shapes shared by api.cpp (the launch) and kernels.hip (__launch_bounds__, unit indexing)
+// launch shapes shared by api.cpp (the launch) and merkle.hip (__launch_bounds__, unit indexing)
 #define P2V_PLAN_WAVES 16  // waves per k_merkle_plan work-group (one global atomic per work-group and bucket)
 #define P2V_FIX_BLOCKS 256 // k_merkle_fix grid: its blocks wait for free slots beside the other batch's kernels
 
@@ -92,20 +92,20 @@ struct DevCircuit {
   uint64_t* vparts;                // [n_vitems][2r][B]: per-item partial alpha-sums
   uint64_t* lutre;                 // [r][nluts][B]: evalFinalRE values (debug trace)
   uint64_t* lutpart;               // [r][n_lut_pieces][B]: k_lut partial sums
-  // Merkle paths with every shared node hashed once (kernels.hip k_merkle_plan / k_merkle_cse /
+  // Merkle paths with every shared node hashed once (merkle.hip k_merkle_plan / k_merkle_cse /
   // k_merkle_fix / k_merkle_resolve; mcse = 0: k_merkle, one full path per lane)
   int32_t mcse;
   int64_t mcap;                    // chains per bucket (T * Q * Bmax)
-  uint32_t* mplan;                 // [1 + S][Q][B]: e | owner << 4 | same_leaf << 9 | root << 10
+  uint32_t* mplan;                 // [1 + S][Q][B]: plan words (merkle.hip plan_pack: e, owner, same_leaf, root)
   uint64_t* mfol;                  // [1 + S][Q][B]: per owned level l, bits 5l..5l+4: the follower (31: none)
-  uint32_t* mchain;                // [depth0 + 1][mcap]: chain ids t << 27 | q << 22 | p, bucket = chain length
+  uint32_t* mchain;                // [depth0 + 1][mcap]: chain ids (merkle.hip entry_pack: t, q, p), bucket = chain length
   int32_t* mcount;                 // [depth0 + 1] x 16: chains per bucket, 64 B apart (k_merkle_resolve zeroes them)
   int32_t* mfixn;                  // flagged followers listed in mfix (k_merkle_resolve zeroes it)
   uint32_t* mfix;                  // [mcap]: chain ids of the followers k_merkle_fix re-runs
   uint8_t* mbadq;                  // [T][Q][B]: the follower failed a shared-node check
   uint64_t* mnode;                 // [T][Q][4][B]: a follower's node at its meeting level
   // Known openings of tree 0 (constants/sigmas: the circuit's tree, its cap in the verifier key),
-  // kernels.hip k_merkle_known / k_merkle_known_miss.  kmode of a run: 0 none (tree 0 with the other
+  // merkle.hip k_merkle_known / k_merkle_known_miss.  kmode of a run: 0 none (tree 0 with the other
   // trees, as ever), 1 probe and insert, 2 probe only.  With kmode != 0, kskip = 1: the leaf units
   // (leaf_order holds nleaf = T - 1 trees) and the shared-node kernels leave tree 0 out.
   int32_t kmode, kskip, nleaf;
@@ -113,7 +113,7 @@ struct DevCircuit {
   uint64_t* krows;                 // [2^lde_bits][kwords], per circuit and device; zero until inserted, then constant
   uint32_t* kvalid;                // [2^lde_bits]: P2V_KNOWN_EMPTY / _VALID / _BUSY
   unsigned long long* kstat;       // per circuit and device: hits, misses, rows inserted
-  uint32_t* kmiss;                 // [Q][B] of this workspace: the run's missed openings q << 22 | p
+  uint32_t* kmiss;                 // [Q][B] of this workspace: the run's missed openings (entry_pack, t = 0)
   int32_t* kmissn;                 // entries of kmiss (k_status zeroes it for the next run)
   // Gate programs (include/p2v.h "gate programs", vanish_prog.hip): the lowered programs of the
   // circuit's G_PROGRAM gates, concatenated; gate g's starts at gprog[gate_poff[g]] (-1: none) with

@@ -1,4 +1,4 @@
-"""CPU model of the shared-node Merkle paths (kernels.hip k_merkle_plan / k_merkle_cse /
+"""CPU model of the shared-node Merkle paths (merkle.hip k_merkle_plan / k_merkle_cse /
 k_merkle_fix / k_merkle_resolve), restated line for line in Python over a stand-in 2-to-1 hash.
 
 The exactness argument does not depend on the hash, so a keyed stand-in is enough to hold the

@@ -494,6 +494,38 @@ def _merkle_top_cases(gc, base_txt, qidx, info, rnd, n_random=40):
     return [json.dumps(d, separators=(",", ":")).encode() for d in cases]
 
 
+_top_campaigns = {}
+
+
+def _merkle_top_campaign(p2v, nb):
+    """The campaign of _merkle_top_cases on the real circuit of 2^nb rows with the oracle's status
+    and trace of every case: computed once, shared by the tests below, never changed."""
+    import random
+    from support import trace_offsets
+    if nb not in _top_campaigns:
+        O = oracle()
+        gc = gen_circuit(nb, 4, 0, 1, 28, 16, 0, 1)
+        base = gc.proof(1, 1)
+        info = p2v.VerifierCircuitData.from_json(gc.common, gc.vkey).info
+        st, tr = O.verify_json(gc.common, gc.vkey, base, trace=True)
+        assert st == 1
+        off = trace_offsets(info.num_challenges, info.num_fri_steps, info.num_query_rounds)["query_idx"]
+        qidx = [int(x) for x in tr[off: off + info.num_query_rounds]]
+        cases = [base] + _merkle_top_cases(gc, base, qidx, info, random.Random(nb))
+        ref = [O.verify_json(gc.common, gc.vkey, c, trace=True) for c in cases]
+        _top_campaigns[nb] = gc, cases, [r[0] for r in ref], np.array([r[1] for r in ref])
+    return _top_campaigns[nb]
+
+
+def _gpu_equals(p2v, gc, cases, sts, otrs):
+    """One batch of `cases` on the GPU: statuses and full traces equal the given oracle words."""
+    vk = p2v.VerifierCircuitData.from_json(gc.common, gc.vkey)
+    res, tr = p2v.BatchVerifier(vk, 0, len(cases)).run(vk.pack_many(cases), trace=True)
+    for i in range(len(cases)):
+        assert res[i] == sts[i], (i, int(res[i]), sts[i])
+        assert np.array_equal(tr[i], otrs[i]), (i, np.nonzero(tr[i] != otrs[i])[0][:10])
+
+
 @pytest.mark.parametrize("cse", [1, 0])
 @pytest.mark.parametrize("nb", [6, 8, 12])
 def test_gpu_merkle_top_level_mutations_vs_oracle(p2v, nb, cse, monkeypatch):
@@ -501,24 +533,25 @@ def test_gpu_merkle_top_level_mutations_vs_oracle(p2v, nb, cse, monkeypatch):
     (Hash/Merkle.hs:27-42): mutations of siblings on nodes shared by several queries of one
     proof, the same change in two queries on one node, bottom values, random changes.  Every
     status and trace word equals the oracle's; the campaign reaches the Merkle failure classes.
-    cse=1: the shared-node paths (kernels.hip k_merkle_plan / k_merkle_cse / k_merkle_resolve, the
+    cse=1: the shared-node paths (merkle.hip k_merkle_plan / k_merkle_cse / k_merkle_resolve, the
     default), whose follower checks (A) (B) (C) these mutations hit on both sides of a meeting
     node; cse=0: k_merkle, one full path per lane.  The batch (> 64 proofs) takes the batch path."""
-    import random
-    from support import trace_offsets
     monkeypatch.setenv("P2V_MERKLE_CSE", str(cse))
-    O = oracle()
-    gc = gen_circuit(nb, 4, 0, 1, 28, 16, 0, 1)
-    base = gc.proof(1, 1)
-    vk = p2v.VerifierCircuitData.from_json(gc.common, gc.vkey)
-    info = vk.info
-    st, tr = O.verify_json(gc.common, gc.vkey, base, trace=True)
-    assert st == 1
-    off = trace_offsets(info.num_challenges, info.num_fri_steps, info.num_query_rounds)["query_idx"]
-    qidx = [int(x) for x in tr[off: off + info.num_query_rounds]]
-    cases = [base] + _merkle_top_cases(gc, base, qidx, info, random.Random(nb))
+    gc, cases, sts, otrs = _merkle_top_campaign(p2v, nb)
     assert len(cases) > 64
-    sts, _ = _gpu_vs_oracle(p2v, gc, cases)
+    _gpu_equals(p2v, gc, cases, sts, otrs)
+    assert {-1, -2} <= set(sts), sorted(set(sts))
+
+
+def test_gpu_merkle_top_level_mutations_latency_mode(p2v):
+    """The same campaign through k_merkle_row (merkle.hip): one batch of at most 64 proofs takes the
+    latency path, every tree's paths in the row form, the step trees with their shifted indices
+    included.  The first 64 cases of the nb = 6 campaign reach no step tree (the oracle gives them
+    1 and -1 only), so the batch is every second case, 59 of the 118: it reaches -1 and -2."""
+    gc, cases, sts, otrs = _merkle_top_campaign(p2v, 6)
+    cases, sts, otrs = cases[::2], sts[::2], otrs[::2]
+    assert len(cases) <= 64
+    _gpu_equals(p2v, gc, cases, sts, otrs)
     assert {-1, -2} <= set(sts), sorted(set(sts))
 
 
@@ -556,7 +589,7 @@ def test_gpu_merkle_shared_nodes_many_proofs(p2v, nb, lk, mode, monkeypatch):
 def test_gpu_merkle_fix_list_full_batch_of_garbage(p2v, monkeypatch):
     """a full batch of garbage proofs flags about half of all (tree, query, proof)
     paths as followers to re-run, many of them twice (their owner's check (B) and their own (A)/(C)).
-    Each path is listed once (kernels.hip cse_flag), the list cannot overflow, and the long list runs
+    Each path is listed once (merkle.hip cse_flag), the list cannot overflow, and the long list runs
     in the lane form of k_merkle_fix.  A valid proof with one follower's sibling corrupted above its
     meeting level (only check (C) sees it) in the last slot, after a run in which every status of
     the workspace was 1, must still be rejected exactly as the oracle rejects it; every status and

@@ -170,6 +170,48 @@ def test_gpu_keyed_forced_variants(p2v, name, value):
         check(res, tr, want_st, want_tr)
 
 
+def test_gpu_keyed_flagged_followers_row_form(p2v):
+    """Flagged followers of a keyed run through the short-list row form of k_merkle_fix
+    (csrc/merkle.hip): tree 0's cap entry is then read from each lane's own key.  130 valid proofs,
+    each under its own key (above the latency mode; a keyed run keeps no known openings, so tree 0
+    goes through plan / chains / fix); eight of them carry one follower's top-level sibling bumped,
+    which only check (C) sees (as tests/test_gpu.py test_gpu_merkle_fix_list_full_batch_of_garbage),
+    in tree 0 (four proofs) and tree 2 (four).  Eight list entries are far below the switch to the
+    lane form.  Statuses and traces equal the oracle's, with shared-node paths and without."""
+    import json
+    from support import P, trace_offsets
+    O = oracle()
+    D = data(p2v)
+    info = D.vk.info
+    off = trace_offsets(info.num_challenges, info.num_fri_steps, info.num_query_rounds)["query_idx"]
+    n = 130
+    ids = np.array([i % 3 for i in range(n)], dtype=np.uint32)
+    rows = np.ascontiguousarray(D.packed[ids])   # proof k is the valid proof of circuit k
+    want_st, want_tr = D.st[ids, ids].copy(), D.tr[ids, ids].copy()
+    assert (want_st == 1).all()
+    slots = [0, 7, 20, 63, 64, 65, 100, 129]   # both sides of a tile edge, the last (partial) tile
+    for i, slot in enumerate(slots):
+        k, tree = int(ids[slot]), (0 if i < 4 else 2)
+        qidx = [int(x) for x in D.tr[k, k][off: off + info.num_query_rounds]]
+        d = json.loads(D.texts[k])
+        qr = d["proof"]["opening_proof"]["query_round_proofs"]
+        lvl = len(qr[0]["initial_trees_proof"]["evals_proofs"][tree][1]["siblings"]) - 1
+        # followers whose node at the top level is a lower query's too: they meet their owner below it
+        fol = [q for q in range(1, len(qidx)) if any(qidx[h] >> lvl == qidx[q] >> lvl for h in range(q))]
+        e = qr[fol[i % len(fol)]]["initial_trees_proof"]["evals_proofs"][tree][1]["siblings"][lvl]["elements"]
+        e[i % 4] = (e[i % 4] + 1) % P
+        text = json.dumps(d, separators=(",", ":")).encode()
+        c, pr = O.circuit(D.common, D.keys[k]), O.proof(text)
+        want_st[slot], want_tr[slot] = O.verify(c, pr, trace=True)
+        O.L.or_proof_free(pr)
+        O.L.or_circuit_free(c)
+        rows[slot] = D.vk.pack_many([text])[0]
+    assert (want_st[slots] == -1).all() and (np.delete(want_st, slots) == 1).all()
+    for cse in ("1", "0"):
+        res, tr = _with_env("P2V_MERKLE_CSE", cse, lambda: p2v.BatchVerifier(D.vk, 0, n).run(rows, trace=True, key_ids=ids))
+        check(res, tr, want_st, want_tr)
+
+
 @pytest.mark.parametrize("form", [None, "lane", "pair"])
 def test_gpu_keyed_lookahead_two_batches(p2v, form):
     """P2V_FLAG_LOOKAHEAD (k_transcript* on the transcript stream): two batches back to back on one

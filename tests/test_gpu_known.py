@@ -1,4 +1,4 @@
-"""GPU tests (MI355X) of the known-openings table of the constants/sigmas tree (kernels.hip
+"""GPU tests (MI355X) of the known-openings table of the constants/sigmas tree (merkle.hip
 k_merkle_known / k_merkle_known_miss, include/p2v.h p2v_circuit_known_stats).
 
 The table is exact memoisation, so every status and trace word must equal the oracle's and those

@@ -1,4 +1,4 @@
-"""CPU model of the known-openings table (kernels.hip k_merkle_known / k_merkle_known_miss),
+"""CPU model of the known-openings table (merkle.hip k_merkle_known / k_merkle_known_miss),
 restated in Python over a stand-in hash.
 
 The table remembers the complete input (leaf words, sibling words) of tree-0 openings that the
