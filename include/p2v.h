@@ -457,11 +457,13 @@ int  p2v_verify_batch_devices(const p2v_circuit* c, const uint64_t* proofs, size
  *         reduction's rare carry fix-up included; b, 24 words, shared by all items) (Poseidon.hs:100-101)
  *   ops 5-8: out[i] = a[i]^7 mod p, canonical, through each S-box form with its rare -2^64
  *         fix-up (Poseidon.hs:92-96): 5 the throughput permutation's (one S-box), 6 its grouped
- *         pair (a[i], b[i]) -> out[2i], out[2i+1], 7 the row form's, 8 the quad / pair forms'
- *   ops 9-11: out[12i..] = the Poseidon permutation of a[12i..] in the latency forms of the
+ *         pair (a[i], b[i]) -> out[2i], out[2i+1], 7 the latency forms' S-box, 8 their chain
+ *         S-box split over a lane pair
+ *   ops 9-10: out[12i..] = the Poseidon permutation of a[12i..] in the latency forms of the
  *         transcript and the small-batch Merkle paths: 9 row (16 lanes per state), 10 quad
- *         (4 lanes), 11 pair (2 lanes)                     (Hash/Poseidon.hs:42-46)
- * Inputs of ops 0-11 may be any u64 (values >= p are congruent, as the reference reads them).
+ *         (4 lanes)                                        (Hash/Poseidon.hs:42-46)
+ *   op 11 (the retired pair form's permutation) is refused with P2V_E_ARG.
+ * Inputs of ops 0-10 may be any u64 (values >= p are congruent, as the reference reads them).
  *
  * Ops 12-20: the F / F^2 arithmetic and the FRI query code of k_fri and the vanishing kernels,
  * each op the production function itself, one lane per item; a = n items of the stated words,

@@ -22,16 +22,12 @@
 
 extern "C" __global__ void k_phase1(DevCircuit, int, int);
 extern "C" __global__ void k_phase1_lane(DevCircuit, int, int);
-extern "C" __global__ void k_phase1_pair(DevCircuit, int, int);
 extern "C" __global__ void k_transcript(DevCircuit, int);
 extern "C" __global__ void k_transcript_lane(DevCircuit, int);
-extern "C" __global__ void k_transcript_pair(DevCircuit, int);
 extern "C" __global__ void k_phase1_keyed(DevCircuit, int, int);
 extern "C" __global__ void k_phase1_lane_keyed(DevCircuit, int, int);
-extern "C" __global__ void k_phase1_pair_keyed(DevCircuit, int, int);
 extern "C" __global__ void k_transcript_keyed(DevCircuit, int);
 extern "C" __global__ void k_transcript_lane_keyed(DevCircuit, int);
-extern "C" __global__ void k_transcript_pair_keyed(DevCircuit, int);
 extern "C" __global__ void k_leaf(DevCircuit);
 extern "C" __global__ void k_merkle(DevCircuit);
 extern "C" __global__ void k_merkle_row(DevCircuit);
@@ -208,7 +204,7 @@ struct p2v_verifier {
   unsigned la_seq = 0;
   float last_ms[kNumKernels] = {0};
   bool timed = false;               // all of ev[] exist: p2v_verifier_run records them
-  int transcript_mode = 0;          // 0 auto, 1 row, 2 quad, 3 lane, 4 pair (env P2V_TRANSCRIPT)
+  int transcript_mode = 0;          // 0 auto, 1 row, 2 quad, 3 lane (env P2V_TRANSCRIPT)
   int quad_min_batch = 4096;        // auto: quad form from this batch size on (env P2V_QUAD_MIN); round 5: with the
                                     // latency row form (lposeidon.h) the row transcript wins up to 2048 proofs
                                     // (2048: 2.40 against 2.98 ms serial, 1.084 against 1.077 M proofs/s at two in
@@ -749,6 +745,9 @@ int p2v_verifier_chain(p2v_verifier* v, p2v_verifier* prev) {
 
 int p2v_verifier_create(const p2v_circuit* pc, int device, size_t max_batch, p2v_verifier** out) {
   if (!pc || !out || max_batch == 0) return fail(P2V_E_ARG, "null argument / zero batch");
+  // not a silent fall to auto: a measurement would report the default under the pair form's name
+  if (const char* tm = getenv("P2V_TRANSCRIPT"); tm && !strcmp(tm, "pair"))
+    return fail(P2V_E_ARG, "P2V_TRANSCRIPT=pair: the pair transcript form was retired (DESIGN.md §5.7)");
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(P2V_E_NODEVICE, "no HIP device available: libp2v verifies on MI355X only (no CPU fallback)");
   if (device < 0 || device >= ndev) return fail(P2V_E_ARG, "bad device index");
@@ -764,7 +763,7 @@ int p2v_verifier_create(const p2v_circuit* pc, int device, size_t max_batch, p2v
   if (const char* mc = getenv("P2V_MERKLE_CSE")) v->merkle_cse = mc[0] != '0';
   if (const char* kl = getenv("P2V_KNOWN_LEAVES")) v->known_mode = kl[0] == '0' ? 0 : kl[0] == '2' ? 2 : 1;
   if (const char* lx = getenv("P2V_LAT_MAX")) v->lat_max_batch = atoi(lx) >= 0 ? atoi(lx) : v->lat_max_batch;
-  if (const char* tm = getenv("P2V_TRANSCRIPT")) v->transcript_mode = !strcmp(tm, "row") ? 1 : !strcmp(tm, "quad") ? 2 : !strcmp(tm, "lane") ? 3 : !strcmp(tm, "pair") ? 4 : 0;
+  if (const char* tm = getenv("P2V_TRANSCRIPT")) v->transcript_mode = !strcmp(tm, "row") ? 1 : !strcmp(tm, "quad") ? 2 : !strcmp(tm, "lane") ? 3 : 0;
   DevCircuit& d = v->dc;
   memset(&d, 0, sizeof d);
   fill_scalars(C, d);
@@ -889,17 +888,15 @@ void p2v_tile_proofs(const uint64_t* pm, size_t n, size_t W, uint64_t* tiled) {
   }
 }
 
-// the transcript form's kernel (tl lanes per proof; 1: lane, 2: pair, else row / quad): with the
+// the transcript form's kernel (tl lanes per proof; 1: lane, else row / quad): with the
 // leaf hashing in its launch, and on its own (the lookahead path).  A keyed run (d.key_id set)
 // takes the kernels whose digest absorb reads the lane's key; the unkeyed kernels are untouched.
 static void launch_phase1(const DevCircuit& d, int tl, int nt_blocks, int leaf_blocks, hipStream_t s) {
-  auto* k = d.key_id ? (tl == 1 ? k_phase1_lane_keyed : tl == 2 ? k_phase1_pair_keyed : k_phase1_keyed)
-                     : (tl == 1 ? k_phase1_lane : tl == 2 ? k_phase1_pair : k_phase1);
+  auto* k = d.key_id ? (tl == 1 ? k_phase1_lane_keyed : k_phase1_keyed) : (tl == 1 ? k_phase1_lane : k_phase1);
   k<<<nt_blocks + leaf_blocks, 256, 0, s>>>(d, nt_blocks, tl);
 }
 static void launch_transcript(const DevCircuit& d, int tl, int nt_blocks, hipStream_t s) {
-  auto* k = d.key_id ? (tl == 1 ? k_transcript_lane_keyed : tl == 2 ? k_transcript_pair_keyed : k_transcript_keyed)
-                     : (tl == 1 ? k_transcript_lane : tl == 2 ? k_transcript_pair : k_transcript);
+  auto* k = d.key_id ? (tl == 1 ? k_transcript_lane_keyed : k_transcript_keyed) : (tl == 1 ? k_transcript_lane : k_transcript);
   k<<<nt_blocks, 256, 0, s>>>(d, tl);
 }
 // one class of vanishing items, [first, last) of d.vitems: one wave per item and 64-proof tile
@@ -956,7 +953,7 @@ int p2v_verifier_run_keyed(p2v_verifier* v, const uint64_t* proofs, const uint32
   // depend on the challenges, so they fill the GPU while the serial transcripts run)
   // transcript form: the row form (16 lanes/proof) has the lowest latency, the quad form
   // (4 lanes/proof) a lower total cost; batches from 4096 proofs hide the quad latency behind
-  // their leaf hashing.  P2V_TRANSCRIPT=row|quad|lane|pair overrides (measurement).
+  // their leaf hashing.  P2V_TRANSCRIPT=row|quad|lane overrides (measurement).
   // From lane_min_batch on, the lane form (one lane per proof, about half of the quad's issue
   // cycles per proof: 85.9 M against 169.4 M VALU instructions per 4096 proofs, DESIGN.md §7.0,
   // with a ~5.7 ms chain): the batch's leaf hashing in the same launch outlasts the chain, so it
@@ -965,7 +962,6 @@ int p2v_verifier_run_keyed(p2v_verifier* v, const uint64_t* proofs, const uint32
   if (v->transcript_mode == 1) tl = 16;
   else if (v->transcript_mode == 2) tl = 4;
   else if (v->transcript_mode == 3) tl = 1;
-  else if (v->transcript_mode == 4) tl = 2;
   const int nt_blocks = (tl * d.B + 255) / 256;
   // Known openings of tree 0 (merkle.hip k_merkle_known): unkeyed runs above the latency mode with
   // the shared-node paths.  Tree 0 then leaves the leaf units and the plan / chains / resolve; its
@@ -1670,7 +1666,8 @@ static int selftest_prog(int device, const uint64_t* a, const uint64_t* b, uint6
 
 int p2v_selftest(int device, int op, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n) {
   const bool needs_b = op == 0 || op == 3 || op == 4 || op == 6;
-  if (op < 0 || op > 21 || (n && (!a || !out || (needs_b && !b)))) return fail(P2V_E_ARG, "bad op / null argument");
+  // op 11 was the retired pair form's permutation; the ops keep their numbers
+  if (op < 0 || op > 21 || op == 11 || (n && (!a || !out || (needs_b && !b)))) return fail(P2V_E_ARG, "bad op / null argument");
   if (op == 21) return selftest_prog(device, a, b, out, n);
   const int ndev = p2v_device_count();
   if (ndev == 0) return fail(P2V_E_NODEVICE, "no HIP device");
@@ -1688,11 +1685,12 @@ int p2v_selftest(int device, int op, const uint64_t* a, const uint64_t* b, uint6
   SCK(hipMemcpy(da.p, a, n * w * 8, hipMemcpyHostToDevice));
   if (needs_b) SCK(hipMemcpy(db.p, b, bw * 8, hipMemcpyHostToDevice));
   if (op >= 9) {
-    const int lanes = op == 9 ? 16 : op == 10 ? 4 : 2;
+    const int lanes = op == 9 ? 16 : 4;
     hipLaunchKernelGGL(k_selftest_forms, dim3((unsigned)((n * lanes + 255) / 256)), dim3(256), 0, 0, op, (const uint64_t*)da.p,
                        (uint64_t*)dout.p, (int64_t)n);
   } else {
-    hipLaunchKernelGGL(k_selftest, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, op, (const uint64_t*)da.p,
+    const size_t lanes = op == 8 ? 2 : 1;   // op 8: a lane pair per item
+    hipLaunchKernelGGL(k_selftest, dim3((unsigned)((n * lanes + 255) / 256)), dim3(256), 0, 0, op, (const uint64_t*)da.p,
                        (const uint64_t*)db.p, (uint64_t*)dout.p, (int64_t)n);
   }
   SCK(hipGetLastError());

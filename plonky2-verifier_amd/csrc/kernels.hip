@@ -38,7 +38,7 @@ __device__ __forceinline__ void leaf_hash_unit(const DevCircuit& c, int unit, in
 
 // The transcript (Challenge/Verifier.hs:58-103, Challenge/FRI.hs:65-104) is a fixed
 // sequence of absorbs and squeezes for a given circuit; the host compiles it into an op
-// program and one interpreter (transcript() below) runs it for each of the four lane layouts
+// program and one interpreter (transcript() below) runs it for each of the three lane layouts
 // of a proof's duplex state (the forms below).  The ~115 permutations form a strictly serial
 // chain, so per-permutation latency, not throughput, is what counts until the batch's leaf
 // hashing outlasts the chain.
@@ -76,7 +76,7 @@ __device__ __forceinline__ E horner_strided(const DevCircuit& c, int64_t off, in
   return h;
 }
 
-// The four lane layouts of a proof's duplex state.  A form says how many lanes share a proof
+// The three lane layouts of a proof's duplex state.  A form says how many lanes share a proof
 // (2^LOG; lane t of them owns the W state words W t .. W t + W - 1, so t == 0 holds word 0 and
 // writes the challenges), how the state is permuted, how a word (wave-uniform position) reaches
 // every lane, and how the lanes' partial sums of the reduced openings fold into lane 0.  The flags
@@ -134,30 +134,6 @@ struct QuadForm {
   }
 };
 
-// Pair form (pposeidon.h; lane 1 owns rate positions 6, 7): about half of the quad's instructions
-// per proof at a shorter chain than the lane form's (P2V_TRANSCRIPT=pair)
-struct PairForm {
-  static constexpr int W = 6, LOG = 1;
-  static constexpr bool LOAD_FIRST = true, CLAMP = true, SUMS_FIRST = false;
-  const int t;
-  const pp::TLdsP& T;
-  __device__ __forceinline__ void permute(uint64_t (&x)[6]) const { pp::permute(x, t, T); }
-  __device__ __forceinline__ uint64_t get_word(const uint64_t (&x)[6], int pos) const { return pp::get_word(x, pos); }
-  __device__ __forceinline__ void load_pis(const DevCircuit& c, int p, int64_t a, int k, uint64_t (&x)[6]) const {
-#pragma unroll
-    for (int j = 0; j < 6; j++) {   // selects, not divergent stores: x stays in registers
-      const int pos = 6 * t + j;
-      const bool mine = pos < 8 && pos < k;
-      const uint64_t v = ld(c, a + (mine ? pos : 0), p);
-      x[j] = mine ? v : x[j];
-    }
-  }
-  __device__ __forceinline__ E fold(E h, const E (&ap)[2]) const {
-    const E h0{pp::bcast64(h.a, 0), pp::bcast64(h.b, 0)}, h1{pp::bcast64(h.a, 1), pp::bcast64(h.b, 1)};
-    return gl::eadd(h0, gl::emul(ap[0], h1));
-  }
-};
-
 // Lane form: the whole state in one lane's registers, the throughput permutation.  About half of
 // the quad form's VALU instructions per proof (85.9 M against 169.4 M per 4096 proofs, DESIGN.md
 // §7.0), but a chain ~3.5x longer (a lone wave issues its dependent permutation at its own
@@ -186,7 +162,7 @@ struct LaneForm {
   __device__ __forceinline__ E fold(E h, const E (&)[1]) const { return h; }
 };
 
-// The interpreter, written once for the four forms: ONE permutation call site per duplex rule.
+// The interpreter, written once for the three forms: ONE permutation call site per duplex rule.
 // KEYED (a parameter of the launch, api.cpp): the digest is the lane's key's (devcommon.h
 // lane_key()), placed into the empty sponge before the op loop -- the program's first op is always
 // the digest absorb (api.cpp transcript_ops), 4 words into rate positions 0..3 of a zero state --
@@ -296,15 +272,12 @@ __device__ __forceinline__ void transcript(const DevCircuit& c, int p, const F& 
 }
 
 // one workgroup of transcripts: `tl` lanes per proof (16: row form, 4: quad form); FORM 1: the
-// lane form, FORM 2: the pair form (kernels of their own, so that their register demand does
-// not touch the others')
+// lane form (kernels of its own, so that its register demand does not touch the others')
 template <int FORM = 0, bool KEYED = false>
 __device__ __forceinline__ void transcript_block(const DevCircuit& c, int tl, TLdsAny& U) {
   const int g = blockIdx.x * 256 + threadIdx.x;
   if constexpr (FORM == 1) {
     if (g < c.B) transcript<KEYED>(c, g, LaneForm{});
-  } else if constexpr (FORM == 2) {
-    if ((g >> 1) < c.B) transcript<KEYED>(c, g >> 1, PairForm{g & 1, U.p});
   } else if (tl == 16) {
     lp::Row LR;
     lp::init(LR, U.l, threadIdx.x);
@@ -325,7 +298,6 @@ __device__ __forceinline__ void phase1_body(const DevCircuit& c, int nt_blocks, 
   if ((int)blockIdx.x < nt_blocks) {   // block-uniform branch: the whole workgroup fills T
     __builtin_amdgcn_s_setprio(3);
     if constexpr (FORM == 0) tlds_fill_form(T, tl);
-    if constexpr (FORM == 2) pp::tlds_fill(T.p, threadIdx.x, 256);
     transcript_block<FORM, KEYED>(c, tl, T);
     return;
   }
@@ -340,19 +312,12 @@ extern "C" __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_pe
 extern "C" __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) k_phase1_lane(DevCircuit c, int nt_blocks, int tl) {
   phase1_body<1>(c, nt_blocks, tl);
 }
-// the pair-form transcript (P2V_TRANSCRIPT=pair) with the leaf hashing
-extern "C" __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) k_phase1_pair(DevCircuit c, int nt_blocks, int tl) {
-  phase1_body<2>(c, nt_blocks, tl);
-}
-// the three with per-proof verifier keys (p2v_verifier_run_keyed)
+// the two with per-proof verifier keys (p2v_verifier_run_keyed)
 extern "C" __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) k_phase1_keyed(DevCircuit c, int nt_blocks, int tl) {
   phase1_body<0, true>(c, nt_blocks, tl);
 }
 extern "C" __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) k_phase1_lane_keyed(DevCircuit c, int nt_blocks, int tl) {
   phase1_body<1, true>(c, nt_blocks, tl);
-}
-extern "C" __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) k_phase1_pair_keyed(DevCircuit c, int nt_blocks, int tl) {
-  phase1_body<2, true>(c, nt_blocks, tl);
 }
 
 // The same two halves as separate launches, for the transcript lookahead (P2V_FLAG_LOOKAHEAD,
@@ -364,17 +329,11 @@ extern "C" __global__ void __launch_bounds__(256) k_transcript(DevCircuit c, int
   tlds_fill_form(T, tl);
   transcript_block(c, tl, T);
 }
-// the lane and pair forms on their own
+// the lane form on its own
 extern "C" __global__ void __launch_bounds__(256) k_transcript_lane(DevCircuit c, int tl) {
   __builtin_amdgcn_s_setprio(3);
   __shared__ TLdsAny T;
   transcript_block<1>(c, tl, T);
-}
-extern "C" __global__ void __launch_bounds__(256) k_transcript_pair(DevCircuit c, int tl) {
-  __builtin_amdgcn_s_setprio(3);
-  __shared__ TLdsAny T;
-  pp::tlds_fill(T.p, threadIdx.x, 256);
-  transcript_block<2>(c, tl, T);
 }
 // and with per-proof verifier keys
 extern "C" __global__ void __launch_bounds__(256) k_transcript_keyed(DevCircuit c, int tl) {
@@ -387,12 +346,6 @@ extern "C" __global__ void __launch_bounds__(256) k_transcript_lane_keyed(DevCir
   __builtin_amdgcn_s_setprio(3);
   __shared__ TLdsAny T;
   transcript_block<1, true>(c, tl, T);
-}
-extern "C" __global__ void __launch_bounds__(256) k_transcript_pair_keyed(DevCircuit c, int tl) {
-  __builtin_amdgcn_s_setprio(3);
-  __shared__ TLdsAny T;
-  pp::tlds_fill(T.p, threadIdx.x, 256);
-  transcript_block<2, true>(c, tl, T);
 }
 extern "C" __global__ void __launch_bounds__(256) k_leaf(DevCircuit c) {
   const int unit = (int)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -687,17 +640,26 @@ extern "C" __global__ void __launch_bounds__(256) k_status(DevCircuit c, int8_t*
 // (the permutation's row reduction with its grouped carry fix-up).  One lane per item.
 // ops 5-8: the S-box forms x -> x^7 (Hash/Poseidon.hs:92-96) with their rare -2^64 fix-ups
 // (ADVICE r4): 5 sbox_n<1> (throughput permutation, partial rounds), 6 sbox_n<2> on the pair
-// (a[i], b[i]) (full rounds; out[2i], out[2i+1]), 7 sbox_lat_br (the retired DPP row form's), 8 sbox_lat (quad /
-// pair forms); canonical outputs.
+// (a[i], b[i]) (full rounds; out[2i], out[2i+1]), 7 lp::sbox (the row and quad forms' full rounds),
+// 8 lp::sbox_u (their chain S-box, split over a lane pair); canonical outputs.  Op 8 runs two lanes
+// per item (lanes 2i, 2i + 1 hold a[i], the even one stores): sbox_u swaps with its DPP neighbour,
+// so every lane of a launched wave runs it, lanes past n on a copy of item n - 1.
 extern "C" __global__ void __launch_bounds__(256) k_selftest(int op, const uint64_t* a, const uint64_t* b, uint64_t* out, int64_t n) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (op == 8) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    const int64_t item = i >> 1;
+    const uint64_t x = lp::sbox_u(a[item < n ? item : n - 1], (int)(i & 1));
+    if (item < n && !(i & 1)) out[item] = gl::canon(x);
+#endif
+    return;
+  }
   if (i >= n) return;
-  if (op >= 5 && op <= 8) {
+  if (op >= 5 && op <= 7) {
 #if defined(__HIP_DEVICE_COMPILE__)
     if (op == 5) { uint64_t x = a[i]; p2::dv::sbox_n<1>(&x); out[i] = gl::canon(x); }
     else if (op == 6) { uint64_t x[2] = {a[i], b[i]}; p2::dv::sbox_n<2>(x); out[2 * i] = gl::canon(x[0]); out[2 * i + 1] = gl::canon(x[1]); }
-    else if (op == 7) out[i] = gl::canon(p2::sbox_lat_br(a[i]));
-    else out[i] = gl::canon(p2::sbox_lat(a[i]));
+    else out[i] = gl::canon(lp::sbox(a[i]));
 #endif
   } else if (op == 0) {
     out[i] = gl::mul(a[i], b[i]);
@@ -730,15 +692,14 @@ extern "C" __global__ void __launch_bounds__(256) k_selftest(int op, const uint6
   }
 }
 
-// The latency forms of the permutation on caller-chosen states (p2v_selftest ops 9-11; ADVICE
-// r4): 9 the row form (lposeidon.h; 16 lanes per state), 10 the quad form (qposeidon.h, 4 lanes),
-// 11 the pair form (pposeidon.h, 2 lanes).  Every lane of a group takes part in the DPP moves, so
-// lanes past n compute on a copy of state n - 1 and store nothing.  a, out: n states of 12 words.
+// The latency forms of the permutation on caller-chosen states (p2v_selftest ops 9-10; ADVICE
+// r4): 9 the row form (lposeidon.h; 16 lanes per state), 10 the quad form (qposeidon.h, 4 lanes).
+// Every lane of a group takes part in the DPP moves, so lanes past n compute on a copy of state
+// n - 1 and store nothing.  a, out: n states of 12 words.
 extern "C" __global__ void __launch_bounds__(256) k_selftest_forms(int op, const uint64_t* a, uint64_t* out, int64_t n) {
   __shared__ TLdsAny T;
-  if (op == 11) pp::tlds_fill(T.p, threadIdx.x, 256);
-  else tlds_fill_form(T, op == 9 ? 16 : 4);
-  const int lanes = op == 9 ? 16 : op == 10 ? 4 : 2;
+  tlds_fill_form(T, op == 9 ? 16 : 4);
+  const int lanes = op == 9 ? 16 : 4;
   const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
   const int64_t item = g / lanes, src = item < n ? item : n - 1;
   const int t = (int)(g % lanes);
@@ -749,18 +710,10 @@ extern "C" __global__ void __launch_bounds__(256) k_selftest_forms(int op, const
     lp::init(LR, T.l, threadIdx.x);
     const uint64_t x = lp::permute(LR.L < 12 ? s[LR.L] : 0, LR, T.l);
     if (item < n && LR.L < 12) o[LR.L] = x;
-  } else if (op == 10) {
+  } else {
     uint64_t x[3] = {s[3 * t], s[3 * t + 1], s[3 * t + 2]};
     qp::permute(x, t, T.q);
     if (item < n) for (int k = 0; k < 3; k++) o[3 * t + k] = x[k];
-  } else {
-    uint64_t x[6];
-#pragma unroll
-    for (int k = 0; k < 6; k++) x[k] = s[6 * t + k];
-    pp::permute(x, t, T.p);
-    if (item < n)
-#pragma unroll
-      for (int k = 0; k < 6; k++) o[6 * t + k] = x[k];
   }
 }
 

@@ -5,7 +5,6 @@
 #include "devcommon.h"
 #include "qposeidon.h"
 #include "rposeidon.h"
-#include "pposeidon.h"
 #include "lposeidon.h"
 
 namespace p2d {
@@ -41,8 +40,8 @@ __device__ __forceinline__ void leaf_sponge(const DevCircuit& c, int64_t off, in
   }
 }
 
-// the constant tables of the transcript forms, in LDS (qposeidon.h TLds, pposeidon.h TLdsP)
-union TLdsAny { qp::TLds q; pp::TLdsP p; lp::TLdsL l; };
+// the constant tables of the transcript forms, in LDS (qposeidon.h TLds, lposeidon.h TLdsL)
+union TLdsAny { qp::TLds q; lp::TLdsL l; };
 
 // the constant tables of the transcript form in use (tl uniform: 16 the row form, else quad)
 __device__ __forceinline__ void tlds_fill_form(TLdsAny& T, int tl) {

@@ -16,16 +16,9 @@
 
 namespace qp {
 
-// The chain's S-box (latency-bound waves: an instruction's cost is its issue slot, s_nop padding
-// included): the asm-block multiply of lposeidon.h (one statement, one padding per multiply,
-// round 5; p2::sbox_lat, five asm statements per multiply, in the host pass only)
-__device__ __forceinline__ uint64_t sbox_q(uint64_t x) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  return lp::sbox(x);
-#else
-  return p2::sbox_lat(x);
-#endif
-}
+// The S-boxes are lposeidon.h's (latency-bound waves: an instruction's cost is its issue slot, s_nop
+// padding included): lp::sbox, the asm-block multiply (one statement, one padding per multiply,
+// round 5), in the full rounds; lp::sbox_u in the chains (qblock below).
 
 // quad_perm rotation: lane t reads lane (t + D) & 3
 template <int D>
@@ -173,13 +166,12 @@ __device__ __forceinline__ void chain_part(const uint64_t (&X)[4][3], const p2::
 }
 // The chain's S-boxes (inputs the same in all four lanes of the quad): x^3 on lanes 0, 2 and x^4 on
 // lanes 1, 3, swapped and multiplied (lp::sbox_u, round 6): three multiplies per lane instead of
-// four, bit-identical to sbox_q
-__device__ __forceinline__ uint64_t sbox_qu(uint64_t x, int t) { return lp::sbox_u(x, t); }
+// four, bit-identical to lp::sbox
 template <int D>
 __device__ __forceinline__ void qblock(uint64_t x[3], int t, const p2::PBlock& B, const QBlock& Q) {
   // y1 = sbox(word 0) from lane 0; s' = the state with y1 in word 0
   uint64_t y[D + 1];
-  y[1] = sbox_qu(bcast64(x[0], 0), t);
+  y[1] = lp::sbox_u(bcast64(x[0], 0), t);
   x[0] = t == 0 ? y[1] : x[0];
   uint64_t X[4][3];
 #pragma unroll
@@ -191,11 +183,11 @@ __device__ __forceinline__ void qblock(uint64_t x[3], int t, const p2::PBlock& B
   chain_part<1>(X, B, pl[1], ph[1]);
   pl[1] = bcast64(pl[1], 0); ph[1] = bcast64(ph[1], 0);
   if constexpr (D >= 3) { chain_part<2>(X, B, pl[2], ph[2]); pl[2] = bcast64(pl[2], 0); ph[2] = bcast64(ph[2], 0); }
-  y[2] = sbox_qu(p2::mds_reduce(pl[1], ph[1]), t);
+  y[2] = lp::sbox_u(p2::mds_reduce(pl[1], ph[1]), t);
   if constexpr (D >= 4) { chain_part<3>(X, B, pl[3], ph[3]); pl[3] = bcast64(pl[3], 0); ph[3] = bcast64(ph[3], 0); }
   if constexpr (D >= 3) {
     constexpr uint32_t c = p2::mds_coeff(0, 0);
-    y[3] = sbox_qu(p2::mds_reduce(pl[2] + (uint64_t)(uint32_t)y[2] * c, ph[2] + (y[2] >> 32) * c), t);
+    y[3] = lp::sbox_u(p2::mds_reduce(pl[2] + (uint64_t)(uint32_t)y[2] * c, ph[2] + (y[2] >> 32) * c), t);
   }
   // per-lane output-row coefficients, one row at a time (row m + 1's loads overlap row m), the
   // first row's before the last S-box: 17 VGPRs in flight instead of 51
@@ -212,7 +204,7 @@ __device__ __forceinline__ void qblock(uint64_t x[3], int t, const p2::PBlock& B
     const uint64_t al = pl[3] + (uint64_t)(uint32_t)y[2] * h2 + (uint64_t)(uint32_t)y[3] * c;
     const uint64_t ah = ph[3] + (y[2] >> 32) * h2 + (y[3] >> 32) * c;
     load_row(0);
-    y[4] = sbox_qu(p2::mds_reduce(al, ah), t);
+    y[4] = lp::sbox_u(p2::mds_reduce(al, ah), t);
   } else {
     load_row(0);
   }
@@ -259,7 +251,7 @@ __device__ __forceinline__ void permute(uint64_t x[3], int t, const TLds& T) {
     lane_rc(T.rc, rr + 2 <= 30 ? rr + 2 : 30, t, nkl, nkh);   // row 30 of the split table is zero
     uint64_t al[3], ah[3];
 #pragma unroll
-    for (int k = 0; k < 3; k++) x[k] = sbox_q(x[k]);
+    for (int k = 0; k < 3; k++) x[k] = lp::sbox(x[k]);
     mds_acc(x, t, kl, kh, al, ah);
 #pragma unroll
     for (int m = 0; m < 3; m++) x[m] = p2::mds_reduce(al[m], ah[m]);

@@ -829,7 +829,7 @@ def device_selftest(op: int, a: np.ndarray, b: Optional[np.ndarray] = None, devi
     form), Poseidon permutation (op 1, a = [n, 12] states), 2-to-1 compression form (op 2, words
     8..11 taken as 0, words 0..3 returned), one MDS layer (op 4), the S-box forms (ops 5-8, x^7;
     op 6 the grouped pair (a[i], b[i]) -> out [n, 2]) and the latency forms of the permutation
-    (ops 9-11: row, quad, pair) on `device`.  Ops 12-20: the F / F^2 arithmetic and the FRI query
+    (ops 9-10: row, quad) on `device`.  Ops 12-20: the F / F^2 arithmetic and the FRI query
     code (a = [n, item words], b = the op's shared words, out = [n, result words]; see p2v.h).
     Op 21: the gate-program interpreter, b = [nwires, nconsts] + GateProgram.words()."""
     a = np.ascontiguousarray(a, dtype=np.uint64)

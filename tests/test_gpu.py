@@ -248,11 +248,11 @@ def test_gpu_n12_standard_batch_vs_oracle(p2v):
             assert (tr[lanes] == tr[lanes[0]]).all()
 
 
-@pytest.mark.parametrize("form", ["row", "quad", "lane", "pair"])
+@pytest.mark.parametrize("form", ["row", "quad", "lane"])
 @pytest.mark.parametrize("nb,mode,lk,pis", [(6, 1, 0, 4), (6, 0, 2, 0), (8, 1, 0, 19)])
 def test_gpu_transcript_forms_vs_oracle(p2v, form, nb, mode, lk, pis):
-    """The four transcript layouts (16, 4, 2 lanes and 1 lane per proof; api.cpp picks the
-    first two by batch size, P2V_TRANSCRIPT forces any) give the oracle's challenges and statuses: real and
+    """The three transcript layouts (16, 4 lanes and 1 lane per proof; api.cpp picks them
+    by batch size, P2V_TRANSCRIPT forces any) give the oracle's challenges and statuses: real and
     degenerate circuits, lookups, 0 / 4 / 19 public inputs (19: a partial last PI block)."""
     gc = gen_circuit(nb, pis, lk, mode=mode)
     cases = [c[0] for c in _cases(gc)]
@@ -266,6 +266,21 @@ def test_gpu_transcript_forms_vs_oracle(p2v, form, nb, mode, lk, pis):
         else:
             os.environ["P2V_TRANSCRIPT"] = old
     assert 1 in sts and any(s != 1 for s in sts)
+
+
+def test_gpu_retired_transcript_form_is_refused(p2v, monkeypatch):
+    """P2V_TRANSCRIPT=pair (the retired pair form) does not fall silently to the
+    default layout: creating a verifier is P2V_E_ARG.  The same circuit verifies once the variable
+    is cleared."""
+    gc = gen_circuit(6, 4, 0, mode=1)
+    vk = p2v.VerifierCircuitData.from_json(gc.common, gc.vkey)
+    monkeypatch.setenv("P2V_TRANSCRIPT", "pair")
+    with pytest.raises(p2v.P2VError) as e:
+        p2v.BatchVerifier(vk, 0, 2)
+    assert e.value.code == p2v.E_ARG and "pair" in e.value.message and "5.7" in e.value.message
+    monkeypatch.delenv("P2V_TRANSCRIPT")
+    packed = vk.pack_many([gc.proof(1, 1), gc.proof(1, 2, flags=1)])
+    assert list(p2v.BatchVerifier(vk, 0, 2).run(packed)) == [1, -3]
 
 
 @pytest.mark.parametrize("nb,mode,lk", [(6, 1, 0), (6, 0, 2), (8, 1, 0)])
@@ -330,7 +345,7 @@ def test_gpu_chained_workspaces(p2v):
 
 
 @pytest.mark.parametrize("B,tiled,mixed,form", [(200, False, False, None), (2048, True, False, None), (1, False, True, None),
-                                                 (64, True, True, None), (2048, True, True, "lane"), (256, False, True, "pair")])
+                                                 (64, True, True, None), (2048, True, True, "lane"), (256, False, True, None)])
 def test_gpu_transcript_lookahead(p2v, B, tiled, mixed, form):
     """P2V_FLAG_LOOKAHEAD: each batch's transcript runs on the workspace's own transcript stream
     into one of two challenge buffers, ahead of the workspace's earlier batches.  Two workspaces,
@@ -340,7 +355,8 @@ def test_gpu_transcript_lookahead(p2v, B, tiled, mixed, form):
     transcript and the tiled layout, B = 200 the row transcript; B = 1 and 64 are latency mode
     (k_fri and the coset / misc vanishing kernels on streams of their own, waiting on the
     lookahead's events), with lookahead and plain runs interleaved on each workspace (mixed;
-    ADVICE r3).  form: the lane / pair transcript layouts (P2V_TRANSCRIPT) on the lookahead stream."""
+    ADVICE r3); B = 256 is the untiled, mixed case above latency mode.  form: the lane transcript
+    layout (P2V_TRANSCRIPT) on the lookahead stream."""
     import torch
     gc = gen_circuit(6, 4, 0, 1, 28, 16, 0, 1)
     vk = p2v.VerifierCircuitData.from_json(gc.common, gc.vkey)
@@ -1298,11 +1314,13 @@ def test_gpu_mds_layer_carry_fixup(p2v):
 
 
 def test_gpu_sbox_forms_edge_values(p2v):
-    """every S-box form (the throughput permutation's single and grouped S-boxes, the row
-    form's, the quad / pair forms') against x^7 mod p on the inputs whose products take the device
-    multiply's rare -2^64 fix-up (2^48 -> 2^96, ...): 2^k, 2^k +- 1, p - 2^k, p - 1, in lanes
-    mixed with random values, so the wave-uniform fix-up branch runs with some lanes needing it and
-    others not."""
+    """every S-box form (the throughput permutation's single and grouped S-boxes, the
+    latency forms' lp::sbox and their chain S-box lp::sbox_u split over a lane pair) against x^7
+    mod p on the inputs whose products take the device multiply's rare -2^64 fix-up (2^48 -> 2^96,
+    ...): 2^k, 2^k +- 1, p - 2^k, p - 1, in lanes mixed with random values, so the wave-uniform
+    fix-up branch runs with some lanes needing it and others not.  The latency forms' ops also run
+    on the first 1 and 65 values: a lone item (op 8: its partner lane and 62 idle lanes) and 130
+    lanes (op 8 crosses a wave edge into a part-filled last wave)."""
     from support import sbox_edge_values
     ev = sbox_edge_values()
     rng = np.random.default_rng(17)
@@ -1315,6 +1333,11 @@ def test_gpu_sbox_forms_edge_values(p2v):
         out = p2v.device_selftest(op, a)
         bad = np.nonzero(out != exp)[0]
         assert len(bad) == 0, [(op, hex(int(a[i])), hex(int(out[i])), hex(int(exp[i]))) for i in bad[:5]]
+    assert len(a) > 65
+    for op in (7, 8):
+        for n in (1, 65):
+            out = p2v.device_selftest(op, a[:n].copy())
+            assert out.shape == (n,) and np.array_equal(out, exp[:n]), (op, n)
     b = a[::-1].copy()
     out = p2v.device_selftest(6, a, b)
     assert np.array_equal(out[:, 0], exp) and np.array_equal(out[:, 1], exp[::-1])
@@ -1323,8 +1346,8 @@ def test_gpu_sbox_forms_edge_values(p2v):
 def test_gpu_permutation_forms_first_round_wrap(p2v):
     """states whose round-0 S-box inputs are exactly the wrap-taking edge values (state
     word = edge value - rc0[i], so state + rc0 = 2^48, ...), plus the KAT and random states, through
-    the throughput permutation (op 1) and the transcript / small-batch latency forms (row, quad,
-    pair: ops 9-11), against the oracle's permutation (Hash/Poseidon.hs:42-46)."""
+    the throughput permutation (op 1) and the transcript / small-batch latency forms (row, quad:
+    ops 9-10), against the oracle's permutation (Hash/Poseidon.hs:42-46)."""
     from support import KAT_IN, KAT_OUT, first_round_wrap_states
     O = oracle()
     rng = np.random.default_rng(23)
@@ -1333,7 +1356,7 @@ def test_gpu_permutation_forms_first_round_wrap(p2v):
     a = np.array(states, dtype=np.uint64)
     exp = np.array([O.permute([int(x) % P for x in st]) for st in states], dtype=np.uint64)
     assert [int(x) for x in exp[0]] == KAT_OUT
-    for op in (1, 9, 10, 11):
+    for op in (1, 9, 10):
         out = p2v.device_selftest(op, a)
         bad = np.nonzero((out != exp).any(axis=1))[0]
         assert len(bad) == 0, (op, [int(i) for i in bad[:5]])

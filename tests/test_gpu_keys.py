@@ -154,9 +154,9 @@ def _with_env(name, value, fn):
             os.environ[name] = old
 
 
-# P2V_TRANSCRIPT modes 1..4 by their names, and the plain one-path-per-lane k_merkle
+# P2V_TRANSCRIPT modes 1..3 by their names, and the plain one-path-per-lane k_merkle
 @pytest.mark.parametrize("name,value", [("P2V_TRANSCRIPT", "row"), ("P2V_TRANSCRIPT", "quad"), ("P2V_TRANSCRIPT", "lane"),
-                                        ("P2V_TRANSCRIPT", "pair"), ("P2V_MERKLE_CSE", "0")])
+                                        ("P2V_MERKLE_CSE", "0")])
 def test_gpu_keyed_forced_variants(p2v, name, value):
     D = data(p2v)
     rows, ids, want_st, want_tr = D.batch(130, seed=130)
@@ -212,7 +212,7 @@ def test_gpu_keyed_flagged_followers_row_form(p2v):
         check(res, tr, want_st, want_tr)
 
 
-@pytest.mark.parametrize("form", [None, "lane", "pair"])
+@pytest.mark.parametrize("form", [None, "lane"])
 def test_gpu_keyed_lookahead_two_batches(p2v, form):
     """P2V_FLAG_LOOKAHEAD (k_transcript* on the transcript stream): two batches back to back on one
     workspace without a host sync in between, with different id arrays."""

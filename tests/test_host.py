@@ -471,3 +471,22 @@ def test_c_abi_argument_contract():
     assert L.p2v_verifier_last_timings(None, (ctypes.c_float * 16)(), 16) == 0
     L.p2v_verifier_free(None)
     L.p2v_circuit_free(None)
+
+
+def test_retired_transcript_form_is_refused_before_any_device_call(monkeypatch):
+    """The retired pair transcript form: its selftest op keeps its number and is
+    P2V_E_ARG in p2v_selftest's first argument check; P2V_TRANSCRIPT=pair is P2V_E_ARG at
+    p2v_verifier_create with a message that names the form, not a silent fall to auto.  Both
+    before any device is looked for."""
+    p2v = p2v_module()
+    L = p2v.lib()
+    assert L.p2v_selftest(0, 11, None, None, None, 0) == p2v.E_ARG
+    assert L.p2v_last_error_message()
+    gc = gen_circuit(6, 4, 0)
+    vk = p2v.VerifierCircuitData.from_json(gc.common, gc.vkey)
+    out = ctypes.c_void_p()
+    monkeypatch.setenv("P2V_TRANSCRIPT", "pair")
+    assert L.p2v_verifier_create(vk.handle, 0, 1, ctypes.byref(out)) == p2v.E_ARG
+    msg = L.p2v_last_error_message().decode()
+    assert "pair" in msg and "retired" in msg and "5.7" in msg
+    assert not out.value

@@ -1,4 +1,4 @@
-"""The split S-box of the latency forms (lposeidon.h lp::sbox_u, qposeidon.h qp::sbox_qu) is
+"""The split S-box of the latency forms (lposeidon.h lp::sbox_u, in the row and the quad chains) is
 bit-identical to lp::sbox.
 
 Even lanes form x^3 = mul_lat(x, x^2), odd lanes x^4 = mul_lat(x^2, x^2), they swap and multiply,

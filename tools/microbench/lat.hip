@@ -9,6 +9,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include "../../plonky2-verifier_amd/csrc/poseidon.h"
+#include "../../plonky2-verifier_amd/csrc/lposeidon.h"
 
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("HIP error %s at %d\n", hipGetErrorString(e_), __LINE__); exit(1); } } while (0)
 
@@ -41,6 +42,14 @@ __device__ __forceinline__ uint64_t mul_v1(uint64_t a, uint64_t b) {
   return gl::mul_nc_dev_v<1>(a, b);
 #else
   return a * b;
+#endif
+}
+// the latency forms' S-box (lposeidon.h: the asm-block multiply), device-only
+__device__ __forceinline__ uint64_t sbox_l(uint64_t x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return lp::sbox(x);
+#else
+  return x;
 #endif
 }
 // the multiply in plain C, no inline asm (so no s_nop padding) and no carry flags: the
@@ -77,7 +86,7 @@ __global__ void __launch_bounds__(256) k_lat(uint64_t* out, uint64_t seed) {
     if constexpr (OP == 4) { X8(x = p2::mul_nc(x, x);) }
     if constexpr (OP == 5) { X8(x = p2::mul_nc(x, x); y = p2::mul_nc(y, y);) }
     if constexpr (OP == 6) { X8(x = p2::mul_nc(x, x); y = p2::mul_nc(y, y); z = p2::mul_nc(z, z); w = p2::mul_nc(w, w);) }
-    if constexpr (OP == 7) { X8(x = p2::sbox_lat(x);) }
+    if constexpr (OP == 7) { X8(x = sbox_l(x);) }
     if constexpr (OP == 8) { X8(x = gl::mul(x, x);) }
     if constexpr (OP == 10) { X8(x = mul_v1(x, x);) }
     if constexpr (OP == 11) { X8(x = mul_v3(x, x);) }
@@ -119,7 +128,7 @@ int main() {
   run<4>("mul_nc chain (x*x)", 8, d);
   run<5>("2 interleaved mul chains", 8, d);
   run<6>("4 interleaved mul chains", 8, d);
-  run<7>("sbox_lat chain", 8, d);
+  run<7>("lp::sbox chain", 8, d);
   run<8>("gl::mul chain (canonical)", 8, d);
   run<10>("mul_nc_dev (V=1) chain", 8, d);
   run<11>("mul_v3 chain (VALU carries)", 8, d);
