@@ -695,6 +695,12 @@ static void gate_coset(const evars_t* V, const gate_t* g, clist* out) {   /* Cus
     long long pos = first;
     while (pos < npts) { long long e = pos + (degree - 1); if (e > npts) e = npts; cs[nchunks] = pos; ce[nchunks] = e; nchunks++; pos = e; if (degree - 1 <= 0) fail(P2V_ERR_CIRCUIT, "partition: non-positive chunk"); }
   }
+  /* chunks = zip3 chunked_domain chunked_values chunked_weights: a short weight list has fewer chunks */
+  {
+    long long nw = g->nweights, wfirst = degree < nw ? degree : nw;
+    long long nchunks_w = 1 + (nw - wfirst + (degree - 2)) / (degree - 1);
+    if (nchunks_w < nchunks) nchunks = nchunks_w;
+  }
   long long nst = nint + 1 < nchunks ? nint + 1 : nchunks;   /* zipWith worker initials chunks */
   EE* evs = (EE*)malloc((nst + 1) * sizeof(EE)); EE* prs = (EE*)malloc((nst + 1) * sizeof(EE));
   for (long long c = 0; c < nst; c++) {

@@ -1258,10 +1258,13 @@ extern "C" {
 //         set; mode 2: a real circuit over a small gate set (Noop, Constant, PublicInput,
 //         Arithmetic) that fits one selector group.  Real modes choose their own groups.
 // ext / arities (narities > 0): the opt-in plonky2 conventions of the Circuit fields above
-void* p2v_gen_circuit_new3(int degree_bits, int num_pis, int lookups, uint64_t circuit_seed, int num_queries, int pow_bits,
-                           int ngroups, int mode, unsigned ext, const int* arities, int narities) {
+// num_challenges: the number of challenge rounds r (config.num_challenges), 1..4
+void* p2v_gen_circuit_new4(int degree_bits, int num_pis, int lookups, uint64_t circuit_seed, int num_queries, int pow_bits,
+                           int ngroups, int mode, unsigned ext, const int* arities, int narities, int num_challenges) {
   try {
+    if (num_challenges < 1 || num_challenges > 4) throw std::runtime_error("gen: num_challenges must be 1..4");
     auto* C = new Circuit();
+    C->r = num_challenges;
     C->degree_bits = degree_bits; C->num_pis = num_pis; C->circuit_seed = circuit_seed;
     C->ext = ext;
     if ((ext & 1) && narities <= 0) throw std::runtime_error("gen: the MinSize form needs the arity list");
@@ -1293,6 +1296,10 @@ void* p2v_gen_circuit_new3(int degree_bits, int num_pis, int lookups, uint64_t c
     build_circuit(*C);
     return C;
   } catch (std::exception& e) { g_err = e.what(); return nullptr; }
+}
+void* p2v_gen_circuit_new3(int degree_bits, int num_pis, int lookups, uint64_t circuit_seed, int num_queries, int pow_bits,
+                           int ngroups, int mode, unsigned ext, const int* arities, int narities) {
+  return p2v_gen_circuit_new4(degree_bits, num_pis, lookups, circuit_seed, num_queries, pow_bits, ngroups, mode, ext, arities, narities, 2);
 }
 void* p2v_gen_circuit_new2(int degree_bits, int num_pis, int lookups, uint64_t circuit_seed, int num_queries, int pow_bits,
                            int ngroups, int mode) {

@@ -124,6 +124,8 @@ class Generator:
         L.p2v_gen_circuit_new3.restype = vp
         L.p2v_gen_circuit_new3.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_uint64, ctypes.c_int, ctypes.c_int,
                                            ctypes.c_int, ctypes.c_int, ctypes.c_uint, vp, ctypes.c_int]
+        L.p2v_gen_circuit_new4.restype = vp
+        L.p2v_gen_circuit_new4.argtypes = L.p2v_gen_circuit_new3.argtypes + [ctypes.c_int]
         L.p2v_gen_common_json.restype = ctypes.c_char_p
         L.p2v_gen_common_json.argtypes = [vp]
         L.p2v_gen_vkey_json.restype = ctypes.c_char_p
@@ -142,14 +144,17 @@ class Generator:
         L.p2v_gen_last_error.restype = ctypes.c_char_p
         self.L = L
 
-    def circuit(self, degree_bits=12, num_pis=4, lookups=0, seed=1, queries=28, pow_bits=16, ngroups=0, mode=0, ext=0, arities=()):
+    def circuit(self, degree_bits=12, num_pis=4, lookups=0, seed=1, queries=28, pow_bits=16, ngroups=0, mode=0, ext=0, arities=(),
+                num_challenges=2):
         """mode 0: degenerate circuit (every gate filter 0), `ngroups` selector groups (0: 3);
         mode 1: real circuit over the recursion gate set; mode 2: real circuit, small gate set
         in one selector group.  ext / arities: the opt-in plonky2 conventions (P2V_EXT_*: 1 the
         `arities` as fri_params.reduction_arity_bits under MinSize, 2 hiding salts, 4
-        hash_or_noop leaves; `arities` without 1: a Fixed strategy)."""
+        hash_or_noop leaves; `arities` without 1: a Fixed strategy).  num_challenges: the
+        challenge rounds r, 1..4."""
         arr = (ctypes.c_int * max(1, len(arities)))(*arities)
-        h = self.L.p2v_gen_circuit_new3(degree_bits, num_pis, lookups, seed, queries, pow_bits, ngroups, mode, ext, arr, len(arities))
+        h = self.L.p2v_gen_circuit_new4(degree_bits, num_pis, lookups, seed, queries, pow_bits, ngroups, mode, ext, arr, len(arities),
+                                        num_challenges)
         if not h:
             raise RuntimeError(self.L.p2v_gen_last_error().decode())
         return GenCircuit(self, h)
@@ -196,8 +201,9 @@ def generator() -> Generator:
 
 
 @lru_cache(maxsize=16)
-def gen_circuit(degree_bits=6, num_pis=4, lookups=0, seed=1, queries=28, pow_bits=16, ngroups=0, mode=0, ext=0, arities=()) -> GenCircuit:
-    return generator().circuit(degree_bits, num_pis, lookups, seed, queries, pow_bits, ngroups, mode, ext, tuple(arities))
+def gen_circuit(degree_bits=6, num_pis=4, lookups=0, seed=1, queries=28, pow_bits=16, ngroups=0, mode=0, ext=0, arities=(),
+                num_challenges=2) -> GenCircuit:
+    return generator().circuit(degree_bits, num_pis, lookups, seed, queries, pow_bits, ngroups, mode, ext, tuple(arities), num_challenges)
 
 
 # ----------------------------------------------------------------------------- plonky2 bytes
