@@ -335,23 +335,56 @@ int  p2v_verifier_run(p2v_verifier* v, const uint64_t* proofs, size_t n,
  * runs (uniform indices: 97 % of the rows after one 4096-proof batch, 99.9 % after two).  The
  * table is made by the first p2v_verifier_create of the handle on a device, zero-filled, shared
  * by all its workspaces there (concurrent streams included) and freed by p2v_circuit_free.
- * Used by unkeyed runs of more than 64 proofs; keyed runs, smaller (latency-mode) runs and
- * P2V_MERKLE_CSE=0 never touch it.  Read at p2v_verifier_create:
+ * Used by runs of more than 64 proofs; smaller (latency-mode) runs and P2V_MERKLE_CSE=0 never
+ * touch it.
+ * Key tables.  A key fixes the cap, so the same holds per key.  The table of a handle with more
+ * than one key (p2v_circuit_with_keys) has one block of 2^lde_bits rows per key, the row of (key
+ * k, index idx) at k << lde_bits | idx, key 0's block first: unkeyed runs on that handle and the
+ * id-0 proofs of keyed runs share key 0's rows.  Coverage is every key or key 0 alone, never a
+ * subset: openings of an uncovered key would all take the miss list, and an all-miss run measured
+ * 0.862 of a run without a table, worse than none.  A keyed run (p2v_verifier_run_keyed with ids,
+ * p2v_verify_batch_keyed through its chunks) uses the table when the handle has more than one key
+ * and the table covers them all; a proof's id is clamped to num_keys - 1 as everywhere, so what
+ * an out-of-range id (status P2V_ERR_CIRCUIT) teaches the table is a true statement about the
+ * last key.  A keyed call on a ONE-key handle keeps the launch sequence without the table (such a
+ * caller has p2v_verifier_run).  p2v_circuit_with_keys and p2v_circuit_shape_variant return new
+ * handles, and each starts with a cold table of its own.
+ * Warm-up.  With K keys used uniformly a 4096-proof batch of the standard circuit draws
+ * 114 688 / K indices per key over 2^15 rows.  K = 1: 97 % of the rows after one batch, 99.9 %
+ * after two.  K = 16: a row is still empty after m batches with probability e^(-0.219 m), so 99 %
+ * of the rows are filled after 21 batches and 99.9 % after 32; until then a keyed workload runs
+ * nearer the all-miss regime above.
+ * Read at the handle's first p2v_verifier_create on a device (no run allocates anything):
  *   P2V_KNOWN_LEAVES   0: off (the launch sequence without the table); 1: on (default); 2: probe
  *                      but never insert, so every opening misses: the cost of a cold table or a
- *                      hostile batch, for measurement
- *   P2V_KNOWN_MAX_MB   the table is made and used only if it fits (default 128, a policy value)
- * HARD REQUIREMENT for P2V_FLAG_INPUT_DEVICE callers: the batch must not change from the call
- * until the run has completed on its stream.  That was always the contract, but breaking it used
- * to spoil only that run.  A remembered row is copied from the batch AFTER the opening was hashed
- * from an earlier read of the same words, so words changed in between would be stored unhashed
- * and accepted for the life of the circuit handle.  (Batches given in host memory are staged in
- * a buffer of the workspace and cannot change.)
+ *                      hostile batch, for measurement.  Keyed runs alike.
+ *   P2V_KNOWN_MAX_MB   bounds ONE key's rows (default 128, a policy value): if they do not fit
+ *                      there is no table at all
+ *   P2V_KNOWN_KEYED_MAX_MB   bounds all num_keys keys' rows together (default 1024, a policy value
+ *                      like the other, not a measurement: the standard circuit needs 33.9 MB per
+ *                      key, so 1024 MB covers 30 keys, and 16 keys take 543 MB of the card's
+ *                      288 GB).  If they do not fit, the handle gets the one-key table: unkeyed
+ *                      runs use it, keyed runs do not.
+ * HARD REQUIREMENT for P2V_FLAG_INPUT_DEVICE callers: the batch, and the key_ids array of a keyed
+ * run, must not change from the call until the run has completed on its stream.  That was always
+ * the contract, but breaking it used to spoil only that run.  A remembered row is copied from the
+ * batch AFTER the opening was hashed from an earlier read of the same words, so words changed in
+ * between would be stored unhashed and accepted for the life of the circuit handle.  Likewise a
+ * row is filed under an id read after the opening was hashed; the miss kernel reads that id once
+ * and takes both the cap it compares against and the row it writes from that one value, so a
+ * changed id cannot file an opening under a key it was not proved for, but which key a proof of
+ * such a run was verified against is then unspecified.  (Batches and ids given in host memory are
+ * staged in buffers of the workspace and cannot change.)
  * p2v_circuit_known_stats: the handle's counters on `device` since the table was made, out[0]
  * openings accepted from the table, out[1] openings that took the full check, out[2] rows
- * inserted; all 0 where there is no table.  Synchronises the device and, like the verifier entry
- * points, leaves `device` the calling thread's current device: tests and diagnostics only. */
+ * inserted, keyed and unkeyed runs together; all 0 where there is no table.  Synchronises the
+ * device and, like the verifier entry points, leaves `device` the calling thread's current
+ * device: tests and diagnostics only.
+ * p2v_circuit_known_key_rows: the VALID rows of `key` on `device`; 0 where there is no table or
+ * it does not cover the key; P2V_E_ARG for key >= p2v_circuit_num_keys.  Synchronises the device
+ * and copies that key's flags to the host: tests and diagnostics only. */
 int  p2v_circuit_known_stats(const p2v_circuit* c, int device, uint64_t out[3]);
+int  p2v_circuit_known_key_rows(const p2v_circuit* c, int device, uint32_t key, uint64_t* valid_rows);
 
 /* p2v_verifier_run against the circuit's key table: proof i is verified against key key_ids[i]
  * (n entries; a device pointer exactly when P2V_FLAG_INPUT_DEVICE is set, else a host pointer,

@@ -131,9 +131,13 @@ struct Event : Owned<hipEvent_t, hipEventDestroy> {
 struct HostPipe;
 // The circuit's known openings of tree 0 on one device (merkle.hip k_merkle_known): the rows, their
 // flags and the three counters.  Shared by every workspace of the circuit on that device; it warms
-// across runs and never affects a result, only time.
+// across runs and never affects a result, only time.  kkeys: the keys it covers, one block of
+// 2^lde_bits rows each (dev.h krows): every key of the handle's table, or key 0 alone (a one-key
+// handle, or all keys' rows over P2V_KNOWN_KEYED_MAX_MB), never a subset.  Keyed runs use it only
+// when it covers every key.
 struct KnownTable {
   int device = -1;
+  int kkeys = 1;
   DevBuf rows, valid, stat;
 };
 // The circuit handle also owns the verifiers the one-shot entry points (p2v_verify_batch,
@@ -824,20 +828,26 @@ int p2v_verifier_create(const p2v_circuit* pc, int device, size_t max_batch, p2v
     d.mbadq = (uint8_t*)v->m_badq.p; d.mnode = (uint64_t*)v->m_node.p;
   }
   // known openings of tree 0: with the shared-node paths only, and when the table fits its budget
-  // (P2V_KNOWN_MAX_MB, default 128: a policy value).  A leaf that is its own digest is not hashed.
+  // (P2V_KNOWN_MAX_MB, default 128: a policy value, one key's rows).  A leaf that is its own digest
+  // is not hashed.  A handle with a key table gets every key's rows when they fit
+  // P2V_KNOWN_KEYED_MAX_MB together (default 1024, a policy value too), else key 0's alone: a table
+  // of some keys would send every opening of the others through the miss list, which costs more
+  // than no table.  Decided by the handle's first workspace on the device.
   d.nleaf = d.T;
   d.kwords = d.lwidth[0] + 4 * d.depth0;
   if (v->known_mode && d.mcse && !(d.noop_leaves && d.lwidth[0] <= 4)) {
-    size_t budget_mb = 128;
+    size_t budget_mb = 128, keyed_mb = 1024;
     if (const char* mb = getenv("P2V_KNOWN_MAX_MB")) budget_mb = atoll(mb) > 0 ? (size_t)atoll(mb) : 0;
-    const size_t nrows = (size_t)1 << d.lde_bits;
-    const size_t bytes = nrows * ((size_t)d.kwords * 8 + 4);
+    if (const char* mb = getenv("P2V_KNOWN_KEYED_MAX_MB")) keyed_mb = atoll(mb) > 0 ? (size_t)atoll(mb) : 0;
+    const size_t bytes = ((size_t)1 << d.lde_bits) * ((size_t)d.kwords * 8 + 4);   // one key's
     if (bytes <= budget_mb << 20) {
       std::lock_guard<std::mutex> lk(pc->known_mu);
       for (auto& k : pc->known) if (k->device == device) v->known = k.get();
       if (!v->known) {
         auto k = std::make_unique<KnownTable>();
         k->device = device;
+        k->kkeys = d.nkeys > 1 && bytes * (size_t)d.nkeys <= keyed_mb << 20 ? d.nkeys : 1;
+        const size_t nrows = (size_t)k->kkeys << d.lde_bits;
         ACK(k->rows.alloc(nrows * d.kwords * 8)); ACK(k->valid.alloc(nrows * 4)); ACK(k->stat.alloc(64));
         ACK(hipMemset(k->rows.p, 0, nrows * d.kwords * 8)); ACK(hipMemset(k->valid.p, 0, nrows * 4)); ACK(hipMemset(k->stat.p, 0, 64));
         ACK(hipStreamSynchronize(nullptr));   // the first run's stream does not wait for the null stream
@@ -963,11 +973,15 @@ int p2v_verifier_run_keyed(p2v_verifier* v, const uint64_t* proofs, const uint32
   else if (v->transcript_mode == 2) tl = 4;
   else if (v->transcript_mode == 3) tl = 1;
   const int nt_blocks = (tl * d.B + 255) / 256;
-  // Known openings of tree 0 (merkle.hip k_merkle_known): unkeyed runs above the latency mode with
-  // the shared-node paths.  Tree 0 then leaves the leaf units and the plan / chains / resolve; its
-  // statuses come from the probe and the miss kernel at the head of the side stream.
+  // Known openings of tree 0 (merkle.hip k_merkle_known): runs above the latency mode with the
+  // shared-node paths.  Tree 0 then leaves the leaf units and the plan / chains / resolve; its
+  // statuses come from the probe and the miss kernel at the head of the side stream.  A keyed run
+  // takes the table only on a handle with more than one key whose table covers them all (the
+  // kernels index it by the id clamped to nkeys - 1); a keyed run on a one-key handle keeps the
+  // launch sequence it had.
   const bool lat = d.n <= v->lat_max_batch;
-  if (v->known && !key_ids && !lat && d.mcse) {
+  const bool key_rows = !key_ids || (d.nkeys > 1 && v->known && v->known->kkeys == d.nkeys);
+  if (v->known && key_rows && !lat && d.mcse) {
     d.kmode = v->known_mode; d.kskip = 1;
     int k = 0;
     for (int j = 0; j < d.T; j++) if (v->dc.leaf_order[j] != 0) d.leaf_order[k++] = v->dc.leaf_order[j];
@@ -1734,6 +1748,25 @@ int p2v_circuit_known_stats(const p2v_circuit* c, int device, uint64_t out[3]) {
   HCK(hipSetDevice(device));
   HCK(hipDeviceSynchronize());
   HCK(hipMemcpy(out, k->stat.p, 3 * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  return P2V_OK;
+}
+
+int p2v_circuit_known_key_rows(const p2v_circuit* c, int device, uint32_t key, uint64_t* valid_rows) {
+  if (!c || !valid_rows) return fail(P2V_E_ARG, "null argument");
+  *valid_rows = 0;
+  if (key >= c->c.num_keys()) return fail(P2V_E_ARG, "key id past the circuit's key table");
+  const KnownTable* k = nullptr;
+  {
+    std::lock_guard<std::mutex> lk(c->known_mu);
+    for (auto& t : c->known) if (t->device == device) k = t.get();
+  }
+  if (!k || key >= (uint32_t)k->kkeys) return P2V_OK;
+  HCK(hipSetDevice(device));
+  HCK(hipDeviceSynchronize());
+  const size_t nrows = (size_t)1 << c->c.lde_bits;
+  std::vector<uint32_t> flags(nrows);
+  HCK(hipMemcpy(flags.data(), (const uint32_t*)k->valid.p + key * nrows, nrows * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  for (uint32_t f : flags) *valid_rows += f == P2V_KNOWN_VALID;
   return P2V_OK;
 }
 

@@ -110,8 +110,11 @@ struct DevCircuit {
   // (leaf_order holds nleaf = T - 1 trees) and the shared-node kernels leave tree 0 out.
   int32_t kmode, kskip, nleaf;
   int32_t kwords;                  // words of a row: lwidth[0] + 4 depth0 (leaf, then siblings from level 0 up)
-  uint64_t* krows;                 // [2^lde_bits][kwords], per circuit and device; zero until inserted, then constant
-  uint32_t* kvalid;                // [2^lde_bits]: P2V_KNOWN_EMPTY / _VALID / _BUSY
+  // The table has one block of 2^lde_bits rows per covered key, key 0's first: the row of (key k,
+  // index idx) is (int64)k << lde_bits | idx.  kkeys (api.cpp) is nkeys or 1, never a subset; a keyed
+  // run (key_id set) probes the table only when kkeys == nkeys, an unkeyed one reads key 0's block.
+  uint64_t* krows;                 // [kkeys << lde_bits][kwords], per circuit and device; zero until inserted, then constant
+  uint32_t* kvalid;                // [kkeys << lde_bits]: P2V_KNOWN_EMPTY / _VALID / _BUSY
   unsigned long long* kstat;       // per circuit and device: hits, misses, rows inserted
   uint32_t* kmiss;                 // [Q][B] of this workspace: the run's missed openings (entry_pack, t = 0)
   int32_t* kmissn;                 // entries of kmiss (k_status zeroes it for the next run)

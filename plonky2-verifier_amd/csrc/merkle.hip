@@ -473,7 +473,16 @@ extern "C" __global__ void __launch_bounds__(256) k_merkle_resolve(DevCircuit c)
 // the full computation below found True, and an opening whose kwords words equal row idx word for
 // word is accepted without hashing.  Exact memoisation: nothing is assumed of the hash, and an
 // opening that differs from the row in one word (or meets an empty row) takes the reference
-// computation.  Unkeyed runs above the latency mode with shared-node paths only (api.cpp).
+// computation.  Runs above the latency mode with shared-node paths only (api.cpp).
+// Keys.  A key fixes the cap, so the argument holds per key: the table of a handle with a key table
+// has one block of 2^lde_bits rows per key, row (k, idx) at (int64)k << lde_bits | idx, key 0's block
+// first (an unkeyed run and a keyed opening with id 0 share it).  The id is clamped to nkeys - 1 as
+// lane_key() clamps it: what an out-of-range id teaches the table is a true statement about the
+// last key (k_status still answers P2V_ERR_CIRCUIT for that proof).  The miss kernel reads an
+// entry's id ONCE and takes both the cap entry it compares against and the row it claims and
+// writes from that one value, so an opening proved under key A cannot land in key B's rows even
+// if the id array changed under the run.  c.key_id is a kernel argument: the test is wave-uniform,
+// and an unkeyed run takes the scalar cs_cap operands and row idx it always did.
 //   k_merkle_known       16 lanes per (query, proof): flag, then the row against the proof's
 //                        words; loads and compares only.  Hit: mk_ok = 1.  Miss: listed
 //   k_merkle_known_miss  the listed openings in full (leaf sponge, path, cap entry); a True one is
@@ -485,6 +494,33 @@ extern "C" __global__ void __launch_bounds__(256) k_merkle_resolve(DevCircuit c)
 // BUSY, a flag that some lanes of the group see later than others) is a miss: a stale or torn view
 // can only cost the computation, never accept an opening.  Runs of other workspaces on other
 // streams read and fill the same table concurrently under the same rule.
+// The key of lane p's proof: its id clamped as lane_key() clamps it, 0 in an unkeyed run.  One load
+// that the compiler may not repeat (see "Keys" above).
+__device__ __forceinline__ uint32_t known_key(const DevCircuit& c, int p) {
+  if (!c.key_id) return 0;
+  return min(__hip_atomic_load(c.key_id + min(p, c.n - 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), (uint32_t)(c.nkeys - 1));
+}
+__device__ __forceinline__ int64_t known_row(const DevCircuit& c, uint32_t k, uint32_t idx) { return (int64_t)k << c.lde_bits | idx; }
+// cap_root / cap_ok / row_cap_ok of tree 0 under key k (from known_key), not under whatever the id
+// array holds by now
+__device__ __forceinline__ uint64_t key_cap_root(const DevCircuit& c, uint32_t k, uint32_t ci, int i) {
+  return c.key_id ? c.keys[(int64_t)k * (4 * c.cap_len + 4) + ci * 4 + i] : c.cs_cap[ci * 4 + i];
+}
+__device__ __forceinline__ bool key_cap_ok(const DevCircuit& c, uint32_t k, uint32_t idx, const uint64_t (&cur)[4]) {
+  bool ok = idx < (uint32_t)c.cap_len;
+  const uint32_t ci = ok ? idx : 0;
+#pragma unroll
+  for (int i = 0; i < 4; i++) ok = ok && (key_cap_root(c, k, ci, i) == cur[i]);
+  return ok;
+}
+__device__ __forceinline__ bool key_row_cap_ok(const DevCircuit& c, uint32_t k, uint32_t idx, uint64_t cur, int L) {
+  const bool ok = idx < (uint32_t)c.cap_len;
+  const uint32_t ci = ok ? idx : 0;
+  uint64_t root = 0;
+  if (L < 4) root = key_cap_root(c, k, ci, L);
+  const uint64_t eq = (L >= 4 || root == cur) ? 1 : 0;
+  return ok && (rp::get_word(eq, 0) & rp::get_word(eq, 1) & rp::get_word(eq, 2) & rp::get_word(eq, 3));
+}
 extern "C" __global__ void __launch_bounds__(256) k_merkle_known(DevCircuit c) {
   const int lane = threadIdx.x & 63, L = threadIdx.x & 15;
   const int64_t g = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 4;   // the opening: proofs fastest
@@ -492,13 +528,14 @@ extern "C" __global__ void __launch_bounds__(256) k_merkle_known(DevCircuit c) {
   const int64_t gg = live ? g : 0;
   const int p = (int)(gg % c.n), q = (int)(gg / c.n);
   const uint32_t idx = (uint32_t)chal(c, CH_QIDX(c) + q, p);   // < 2^lde_bits: masked by the transcript
+  const int64_t r = known_row(c, known_key(c, p), idx);   // the row of (the lane's key, idx)
   const int64_t base = c.q0 + (int64_t)q * c.qstride;
   const int lw = c.lwidth[0];
   bool bad = !live;
   if (live) {
-    bad = __hip_atomic_load(c.kvalid + idx, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) != P2V_KNOWN_VALID;
+    bad = __hip_atomic_load(c.kvalid + r, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) != P2V_KNOWN_VALID;
     if (!bad) {
-      const uint64_t* row = c.krows + (int64_t)idx * c.kwords;   // lane L: words L, L + 16, ...: 128-B reads of the row
+      const uint64_t* row = c.krows + r * c.kwords;   // lane L: words L, L + 16, ...: 128-B reads of the row
 #pragma unroll 3
       for (int j = L; j < c.kwords; j += 16)
         bad |= row[j] != ld(c, j < lw ? base + c.leaf[0] + j : base + c.path[0] + (j - lw), p);
@@ -519,12 +556,13 @@ extern "C" __global__ void __launch_bounds__(256) k_merkle_known(DevCircuit c) {
   // a miss is k_merkle_known_miss's to decide; one that could not be listed is rejected
   if (live && L == 0 && (!miss || !listed)) mk_at(c, 0, q, p) = miss ? 0 : 1;
 }
-// the row of a True opening: by the one group (or lane, nl = 1) that takes it from EMPTY
-__device__ __forceinline__ void known_insert(const DevCircuit& c, uint32_t idx, int q, int p, int L, int nl, bool mine) {
+// row r (known_row of the key the opening was proved under) of a True opening: by the one group
+// (or lane, nl = 1) that takes it from EMPTY
+__device__ __forceinline__ void known_insert(const DevCircuit& c, int64_t r, int q, int p, int L, int nl, bool mine) {
   const int64_t base = c.q0 + (int64_t)q * c.qstride;
   const int lw = c.lwidth[0];
   if (mine) {
-    uint64_t* row = c.krows + (int64_t)idx * c.kwords;
+    uint64_t* row = c.krows + r * c.kwords;
     for (int j = L; j < c.kwords; j += nl) row[j] = ld(c, j < lw ? base + c.leaf[0] + j : base + c.path[0] + (j - lw), p);
   }
   // each lane's words are complete at device scope after its own fence; the group's lanes then
@@ -536,7 +574,7 @@ __device__ __forceinline__ void known_insert(const DevCircuit& c, uint32_t idx, 
   const uint64_t grp = nl == 1 ? 1ULL << lane : 0xFFFFULL << (lane & 48);
   const uint64_t done = __ballot(mine);
   if (mine && L == 0 && (done & grp) == grp) {
-    __hip_atomic_store(c.kvalid + idx, P2V_KNOWN_VALID, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(c.kvalid + r, P2V_KNOWN_VALID, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
     atomicAdd(c.kstat + 2, 1ULL);
   }
 }
@@ -549,15 +587,17 @@ static __device__ __forceinline__ void lane(const DevCircuit& c, int64_t k) {
   entry_unpack(c.kmiss[k], t, q, p);   // t == 0
   const int64_t base = c.q0 + (int64_t)q * c.qstride;
   const uint32_t idx0 = (uint32_t)chal(c, CH_QIDX(c) + q, p);
+  const uint32_t kk = known_key(c, p);   // read once: the cap below and the row are this key's
   uint64_t st[12];
   leaf_sponge(c, base + c.leaf[0], c.lwidth[0], p, st);
   uint64_t cur[4] = {st[0], st[1], st[2], st[3]};
   uint32_t idx = idx0;
   lane_climb(c, base + c.path[0], 0, c.depth0, p, cur, idx);
-  const bool ok = cap_ok(c, 0, idx, cur, p);
+  const bool ok = key_cap_ok(c, kk, idx, cur);
   mk_at(c, 0, q, p) = ok ? 1 : 0;
-  const bool mine = ok && c.kmode == 1 && atomicCAS(c.kvalid + idx0, P2V_KNOWN_EMPTY, P2V_KNOWN_BUSY) == P2V_KNOWN_EMPTY;
-  known_insert(c, idx0, q, p, 0, 1, mine);
+  const int64_t r = known_row(c, kk, idx0);
+  const bool mine = ok && c.kmode == 1 && atomicCAS(c.kvalid + r, P2V_KNOWN_EMPTY, P2V_KNOWN_BUSY) == P2V_KNOWN_EMPTY;
+  known_insert(c, r, q, p, 0, 1, mine);
 }
 static __device__ __forceinline__ void row(const DevCircuit& c, int64_t k, const lp::Row& LR, const lp::TLdsL& TL) {
   const int L = LR.L;
@@ -566,6 +606,8 @@ static __device__ __forceinline__ void row(const DevCircuit& c, int64_t k, const
   entry_unpack(c.kmiss[k], t, q, p);   // t == 0
   const int64_t base = c.q0 + (int64_t)q * c.qstride;
   const uint32_t idx0 = (uint32_t)chal(c, CH_QIDX(c) + q, p);
+  // read once, and lane 0's value in all 16 lanes: the cap below and the row are this key's
+  const uint32_t kk = c.key_id ? (uint32_t)rp::get_word((uint64_t)known_key(c, p), 0) : 0u;
   // the leaf sponge (Hash/Sponge.hs:26-31; overwrite mode, no padding): lane L < 8 takes word
   // i + L of each block, the other state words stay
   uint64_t x = 0;
@@ -575,13 +617,14 @@ static __device__ __forceinline__ void row(const DevCircuit& c, int64_t k, const
   }
   uint32_t idx = idx0;
   const uint64_t cur = row_climb(c, base + c.path[0], 0, c.depth0, p, LR, TL, L < 4 ? x : 0, idx);
-  const bool ok = row_cap_ok(c, 0, idx, cur, p, L);   // (unkeyed runs only: key 0's cap)
+  const bool ok = key_row_cap_ok(c, kk, idx, cur, L);
   if (L == 0) mk_at(c, 0, q, p) = ok ? 1 : 0;
   if (ok && c.kmode == 1) {   // row-uniform
+    const int64_t r = known_row(c, kk, idx0);
     uint32_t old = P2V_KNOWN_VALID;
-    if (L == 0) old = atomicCAS(c.kvalid + idx0, P2V_KNOWN_EMPTY, P2V_KNOWN_BUSY);
+    if (L == 0) old = atomicCAS(c.kvalid + r, P2V_KNOWN_EMPTY, P2V_KNOWN_BUSY);
     old = (uint32_t)rp::get_word((uint64_t)old, 0);
-    known_insert(c, idx0, q, p, L, 16, old == P2V_KNOWN_EMPTY);
+    known_insert(c, r, q, p, L, 16, old == P2V_KNOWN_EMPTY);
   }
 }
 };

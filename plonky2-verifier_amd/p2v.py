@@ -154,6 +154,7 @@ def lib() -> ctypes.CDLL:
     L.p2v_circuit_with_keys.argtypes = [vp, u64p, sz, ctypes.POINTER(vp)]
     L.p2v_circuit_num_keys.argtypes = [vp]
     L.p2v_circuit_known_stats.argtypes = [vp, ctypes.c_int, u64p]
+    L.p2v_circuit_known_key_rows.argtypes = [vp, ctypes.c_int, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint64)]
     L.p2v_verifier_run_keyed.argtypes = [vp, u64p, vp, sz, i8p, u64p, vp, ctypes.c_uint32]
     L.p2v_verify_batch_keyed.argtypes = [vp, u64p, vp, sz, i8p, ctypes.c_int]
     L.p2v_circuit_from_json_gates.argtypes = [ctypes.c_char_p, sz, ctypes.c_char_p, sz, ctypes.c_uint32,
@@ -450,6 +451,14 @@ class VerifierCircuitData:
         out = np.zeros(3, dtype=np.uint64)
         _check(lib().p2v_circuit_known_stats(self._h, device, out.ctypes.data))
         return {"hits": int(out[0]), "misses": int(out[1]), "inserted": int(out[2])}
+
+    def known_rows(self, key: int, device: int = 0) -> int:
+        """Rows of `key` (an index into the key table) that the table on `device` holds
+        (p2v_circuit_known_key_rows); 0 where there is no table or it does not cover the key,
+        P2VError for key >= num_keys.  Synchronises the device: tests and diagnostics."""
+        out = ctypes.c_uint64(0)
+        _check(lib().p2v_circuit_known_key_rows(self._h, device, key, ctypes.byref(out)))
+        return int(out.value)
 
     @property
     def key_words(self) -> int:

@@ -2,11 +2,16 @@
 """What per-proof verifier keys cost (developer tool; DESIGN.md "Key tables").
 
 The bench's C2 workload -- 4096 proofs of the real degree_bits-12 recursion circuit, resident in
-HBM in the 64-proof tiled layout, two workspaces in flight -- timed in one process in three legs,
+HBM in the 64-proof tiled layout, two workspaces in flight -- timed in one process in five legs,
 alternated so that clock drift hits them alike:
   (a) p2v_verifier_run                      (unkeyed kernels)
   (b) p2v_verifier_run_keyed, every id 0    (keyed kernels, one key)
-  (c) p2v_verifier_run_keyed, 16 keys spread uniformly over the batch
+  (c) p2v_verifier_run_keyed, 16 keys spread uniformly over the batch, the known-openings table
+      on (one block of rows per key), warm
+  (c0) as (c) with P2V_KNOWN_LEAVES=0       (no table: the keyed launch sequence before it)
+  (c2) as (c) with P2V_KNOWN_LEAVES=2       (probe only: every opening misses, the cold regime)
+Each leg has a handle of its own and makes its two workspaces under its own environment (the
+switches are read at p2v_verifier_create); a handle's table stays warm between its leg's passes.
 The circuits of generator seeds 1..16 share their common data (asserted) and differ in their
 key.  Every leg verifies valid proofs, all accepted (checked on the device after every launch):
 (a) and (b) 64 distinct proofs of circuit 1, (c) 4 distinct proofs of each circuit, proof i of
@@ -14,8 +19,11 @@ the batch under key i % 16.  (A proof under a wrong key is not the same work: it
 no longer fit its Merkle paths, so the shared-node checks of k_merkle_cse flag followers that
 k_merkle_fix re-runs.)  Each leg reports proofs/s, the shader clock
 its pass held (clock probes at both ends) and proofs/s per GHz; the spread between the repeated
-(a) legs is the yardstick for (b) and (c).  A closing serial pass gives each leg's per-kernel
-times (p2v_verifier_last_timings).  Prints one JSON line.
+(a) legs is the yardstick for the others.  A closing serial pass gives each leg's per-kernel
+times (p2v_verifier_last_timings), and a cold-start trace the table's hits, misses and inserted
+rows per batch from a cold 16-key handle (--cold-steps).  The trace is of THIS workload, whose
+--per-key distinct proofs per key open few distinct indices; traffic of all-distinct proofs warms
+as derived in include/p2v.h.  Prints one JSON line.
 """
 import argparse
 import concurrent.futures as cf
@@ -38,6 +46,7 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--repeats", type=int, default=3, help="times each leg is run (alternated)")
+    ap.add_argument("--cold-steps", type=int, default=6, help="batches of the cold-start trace")
     args = ap.parse_args()
     import torch
     assert torch.cuda.is_available(), "needs a GPU"
@@ -61,12 +70,31 @@ def main():
     dev = torch.device("cuda", 0)
     d_mixed = torch.from_numpy(p2v.tile_proofs(np.ascontiguousarray(packed[idx])).view(np.int64)).to(dev)
     d_own = torch.from_numpy(p2v.tile_proofs(np.ascontiguousarray(vk.pack_many(texts0)[idx])).view(np.int64)).to(dev)
-    d_rows = {"a": d_own, "b": d_own, "c": d_mixed}
-    d_ids = {"a": None, "b": torch.zeros(B, dtype=torch.int32, device=dev), "c": torch.from_numpy(ids.view(np.int32)).to(dev)}
+    LEGS = ["a", "b", "c", "c0", "c2"]
+    leg_env = {"c0": {"P2V_KNOWN_LEAVES": "0"}, "c2": {"P2V_KNOWN_LEAVES": "2"}}
+    d_zero, d_uniform = torch.zeros(B, dtype=torch.int32, device=dev), torch.from_numpy(ids.view(np.int32)).to(dev)
+    d_rows = {"a": d_own, "b": d_own, "c": d_mixed, "c0": d_mixed, "c2": d_mixed}
+    d_ids = {"a": None, "b": d_zero, "c": d_uniform, "c0": d_uniform, "c2": d_uniform}
     d_ones = torch.ones(B, dtype=torch.int8, device=dev)
-    d_want = {k: d_ones for k in "abc"}
+    d_want = {k: d_ones for k in LEGS}
     nv = 2
-    bvs = [p2v.BatchVerifier(vk, 0, B) for _ in range(nv)]
+    handles = {leg: base.with_keys([c.vkey for c in gcs[1:]]) for leg in LEGS}   # each with its own table
+    bvs = []
+
+    def workspaces(leg, count=nv):
+        """The leg's workspaces, made under its environment; the earlier leg's are freed first."""
+        bvs.clear()
+        env = leg_env.get(leg, {})
+        old = {k: os.environ.get(k) for k in env}
+        os.environ.update(env)
+        try:
+            bvs.extend(p2v.BatchVerifier(handles[leg], 0, B) for _ in range(count))
+        finally:
+            for k, v in old.items():
+                if v is None:
+                    os.environ.pop(k, None)
+                else:
+                    os.environ[k] = v
     streams = [torch.cuda.current_stream(dev), torch.cuda.Stream(dev)]
     d_res = [torch.empty(B, dtype=torch.int8, device=dev) for _ in range(nv)]
     NPROBE = 256
@@ -77,6 +105,7 @@ def main():
                           key_ids=kid.data_ptr() if kid is not None else None)
 
     def timed(leg, steps):
+        workspaces(leg)
         cnt = torch.zeros((nv, 2), dtype=torch.int64, device=dev)
         stamps = torch.zeros((2, NPROBE, 3), dtype=torch.int64, device=dev)
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -101,23 +130,37 @@ def main():
         rate = B * steps / (e0.elapsed_time(e1) * 1e-3)
         return {"proofs_per_s": round(rate, 1), "clock_ghz": ghz, "per_ghz": round(rate / ghz, 1) if ghz else None}
 
-    legs = {k: [] for k in "abc"}
+    legs = {k: [] for k in LEGS}
     for _ in range(args.repeats):
-        for leg in "abc":
+        for leg in LEGS:
             legs[leg].append(timed(leg, args.steps))
     kernels = {}
-    for leg in "abc":   # serial: per-kernel times of the last of a few synchronous runs
+    for leg in LEGS:   # serial: per-kernel times of the last of a few synchronous runs
+        workspaces(leg, 1)
         for _ in range(3):
             launch(leg, 0, True)
         assert bool((d_res[0] == d_want[leg]).all())
         kernels[leg] = {k: round(v, 4) for k, v in bvs[0].last_timings().items()}
+    known = {leg: handles[leg].known_stats() for leg in LEGS}
+    # cold start: a fresh handle (a cold table of all keys), one batch at a time
+    handles["cold"] = base.with_keys([c.vkey for c in gcs[1:]])
+    d_rows["cold"], d_ids["cold"], d_want["cold"] = d_mixed, d_uniform, d_ones
+    workspaces("cold", 1)
+    cold, prev = [], handles["cold"].known_stats()
+    for _ in range(args.cold_steps):
+        launch("cold", 0, True)
+        cur = handles["cold"].known_stats()
+        cold.append({k: cur[k] - prev[k] for k in cur})
+        prev = cur
+    cold_rows = [handles["cold"].known_rows(k) for k in range(K)]
     med = {leg: float(np.median([r["per_ghz"] or 0 for r in legs[leg]])) for leg in legs}
     a = [r["per_ghz"] or 0 for r in legs["a"]]
     out = {"workload": f"{B} proofs, degree_bits {args.degree_bits}, tiled, device-resident, {nv} in flight, {K} keys",
            "steps": args.steps, "legs": legs, "median_per_ghz": {k: round(v, 1) for k, v in med.items()},
            "a_spread_per_ghz": round(max(a) - min(a), 1), "a_spread_rel": round((max(a) - min(a)) / med["a"], 5) if med["a"] else None,
-           "b_over_a": round(med["b"] / med["a"], 5) if med["a"] else None, "c_over_a": round(med["c"] / med["a"], 5) if med["a"] else None,
-           "serial_kernel_ms": kernels}
+           "over_a": {leg: round(med[leg] / med["a"], 5) if med["a"] else None for leg in LEGS if leg != "a"},
+           "c_over_c0": round(med["c"] / med["c0"], 5) if med["c0"] else None,
+           "serial_kernel_ms": kernels, "known_stats": known, "cold_trace": cold, "cold_rows_per_key": cold_rows}
     print(json.dumps(out))
     return 0
 
