@@ -8,7 +8,7 @@
 #define P2V_MAX_R 4
 #define P2V_LUT_CHUNK 16   // baby steps of the LUT evaluation
 #define P2V_LUT_PIECE 256  // chunks per k_lut work unit (4096 table entries)
-// launch shapes shared by api.cpp (the launch) and merkle.hip (__launch_bounds__, unit indexing)
+// launch shapes shared by api_run.cpp (the launch) and merkle.hip (__launch_bounds__, unit indexing)
 #define P2V_PLAN_WAVES 16  // waves per k_merkle_plan work-group (one global atomic per work-group and bucket)
 #define P2V_FIX_BLOCKS 256 // k_merkle_fix grid: its blocks wait for free slots beside the other batch's kernels
 
@@ -111,7 +111,7 @@ struct DevCircuit {
   int32_t kmode, kskip, nleaf;
   int32_t kwords;                  // words of a row: lwidth[0] + 4 depth0 (leaf, then siblings from level 0 up)
   // The table has one block of 2^lde_bits rows per covered key, key 0's first: the row of (key k,
-  // index idx) is (int64)k << lde_bits | idx.  kkeys (api.cpp) is nkeys or 1, never a subset; a keyed
+  // index idx) is (int64)k << lde_bits | idx.  kkeys (api_workspace.cpp) is nkeys or 1, never a subset; a keyed
   // run (key_id set) probes the table only when kkeys == nkeys, an unkeyed one reads key 0's block.
   uint64_t* krows;                 // [kkeys << lde_bits][kwords], per circuit and device; zero until inserted, then constant
   uint32_t* kvalid;                // [kkeys << lde_bits]: P2V_KNOWN_EMPTY / _VALID / _BUSY

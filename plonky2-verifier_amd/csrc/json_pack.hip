@@ -23,6 +23,7 @@
 //     funnel-shifted, unrolled over 21 digit positions).
 // Tokens longer than 20 digits go to the host reader.
 #include "devcommon.h"
+#include "kernels.h"
 
 namespace {
 // 4-bit mask of the bytes of x that are '0'..'9' or '-' (exact for every byte value)

@@ -15,6 +15,7 @@
 //                 (proof, query)  (Plonk/FRI.hs:151-407)
 //   k_status      reference evaluation order -> int8 status (+ optional trace)
 #include "leafhash.h"
+#include "kernels.h"
 
 using namespace p2d;
 using gl::E;
@@ -113,7 +114,7 @@ struct RowForm {
 
 // Quad form (qposeidon.h): higher per-permutation latency than the row form but ~2.3x fewer issue
 // slots in total, which is what matters once the batch is large enough that the transcript hides
-// behind the leaf hashing sharing its launch (the host picks the form, see api.cpp).
+// behind the leaf hashing sharing its launch (the host picks the form, see api_run.cpp).
 struct QuadForm {
   static constexpr int W = 3, LOG = 2;
   static constexpr bool LOAD_FIRST = true, CLAMP = true, SUMS_FIRST = true;
@@ -137,7 +138,7 @@ struct QuadForm {
 // Lane form: the whole state in one lane's registers, the throughput permutation.  About half of
 // the quad form's VALU instructions per proof (85.9 M against 169.4 M per 4096 proofs, DESIGN.md
 // §7.0), but a chain ~3.5x longer (a lone wave issues its dependent permutation at its own
-// latency): for launches whose leaf hashing outlasts it (api.cpp, P2V_TRANSCRIPT=lane).
+// latency): for launches whose leaf hashing outlasts it (api_run.cpp, P2V_TRANSCRIPT=lane).
 struct LaneForm {
   static constexpr int W = 12, LOG = 0;
   static constexpr bool LOAD_FIRST = false, CLAMP = false, SUMS_FIRST = false;
@@ -163,9 +164,9 @@ struct LaneForm {
 };
 
 // The interpreter, written once for the three forms: ONE permutation call site per duplex rule.
-// KEYED (a parameter of the launch, api.cpp): the digest is the lane's key's (devcommon.h
+// KEYED (a parameter of the launch, api_run.cpp): the digest is the lane's key's (devcommon.h
 // lane_key()), placed into the empty sponge before the op loop -- the program's first op is always
-// the digest absorb (api.cpp transcript_ops), 4 words into rate positions 0..3 of a zero state --
+// the digest absorb (api_workspace.cpp transcript_ops), 4 words into rate positions 0..3 of a zero state --
 // so it holds no register beyond the state's.  The unkeyed kernels keep the digest as a scalar
 // operand of the interpreter, and their registers.
 template <bool KEYED, class F>
@@ -321,7 +322,7 @@ extern "C" __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_pe
 }
 
 // The same two halves as separate launches, for the transcript lookahead (P2V_FLAG_LOOKAHEAD,
-// api.cpp): the transcript on a stream of its own, one batch ahead of the leaf hashing.  (As the
+// api_run.cpp): the transcript on a stream of its own, one batch ahead of the leaf hashing.  (As the
 // default form of phase 1 they measured slower: DESIGN.md "Retired run-time switches".)
 extern "C" __global__ void __launch_bounds__(256) k_transcript(DevCircuit c, int tl) {
   __builtin_amdgcn_s_setprio(3);

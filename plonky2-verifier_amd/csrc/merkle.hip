@@ -8,6 +8,7 @@
 //                 already found True; only the openings not in it are hashed
 //   k_merkle_row  latency mode: every path in the row form
 #include "leafhash.h"
+#include "kernels.h"
 
 using namespace p2d;
 
@@ -473,7 +474,7 @@ extern "C" __global__ void __launch_bounds__(256) k_merkle_resolve(DevCircuit c)
 // the full computation below found True, and an opening whose kwords words equal row idx word for
 // word is accepted without hashing.  Exact memoisation: nothing is assumed of the hash, and an
 // opening that differs from the row in one word (or meets an empty row) takes the reference
-// computation.  Runs above the latency mode with shared-node paths only (api.cpp).
+// computation.  Runs above the latency mode with shared-node paths only (api_run.cpp).
 // Keys.  A key fixes the cap, so the argument holds per key: the table of a handle with a key table
 // has one block of 2^lde_bits rows per key, row (k, idx) at (int64)k << lde_bits | idx, key 0's block
 // first (an unkeyed run and a keyed opening with id 0 share it).  The id is clamped to nkeys - 1 as
@@ -639,7 +640,7 @@ extern "C" __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_pe
   list_entries<MissList>(c, nmiss);
 }
 
-// Latency mode (small batches, api.cpp): the same paths in the row form of the permutation
+// Latency mode (small batches, api_run.cpp): the same paths in the row form of the permutation
 // (lposeidon.h: 16 lanes per path, lane L < 12 holding word L), four paths per wave.  A path is a
 // chain of dependent compressions; one lane per path issues at the single-wave latency (~53 us
 // per compression, lat.hip), the row form at ~14 us.  Row = path (tree position, query, proof),

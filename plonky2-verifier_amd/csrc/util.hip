@@ -3,6 +3,7 @@
 // touches a verifier's buffers; both are enqueued on the caller's stream.
 #include <hip/hip_runtime.h>
 #include <cstdint>
+#include "kernels.h"
 
 // counters[0] += #{i < n : results[i] != expect[i]}; counters[1] += 1 (this check ran).  One
 // workgroup-reduced atomic per 256 statuses; expect may be shorter than results' batch only if

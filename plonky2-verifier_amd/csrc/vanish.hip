@@ -2,6 +2,7 @@
 // vanish_poseidon.hip): the lookup-table pieces, the coset-interpolation and misc item classes,
 // and the final sum with the quotient check.  The device programs are in vanish.h.
 #include "vanish.h"
+#include "kernels.h"
 
 using namespace p2d;
 using gl::E;

@@ -11,6 +11,7 @@
 // P2V_PROG_SLOTS slots of two u64 for 64 lanes: 32 KB per one-wave work-group, static.
 // WIRE / CONST / PIHASH / LIT values are operand kinds and occupy no slot.
 #include "vanish.h"
+#include "kernels.h"
 
 using namespace p2d;
 using gl::E;

@@ -2,12 +2,9 @@
 # Measurement / isolation builds of libp2v with extra compile flags, loaded through P2V_LIB:
 #   variants/build.sh <name> "<flags>"   ->   variants/libp2v_<name>.so
 #   w7:    -DP2V_MERKLE_WAVES=7   (k_merkle at a forced 7 waves per SIMD)
+# Built by the Makefile's own rules into variants/build_<name>, so a variant always holds the
+# units the library does.
 set -e
 cd "$(dirname "$0")/.."
 NAME=$1; EXTRA=$2
-F="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wno-unused-result -Werror=inline-asm $EXTRA"
-mkdir -p variants/build_$NAME
-for t in kernels merkle vanish vanish_poseidon vanish_prog json_pack util; do /opt/rocm/bin/hipcc $F -c -o variants/build_$NAME/$t.o csrc/$t.hip & done
-/opt/rocm/bin/hipcc $F -x hip -c -o variants/build_$NAME/api.o csrc/api.cpp &
-wait
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o variants/libp2v_$NAME.so variants/build_$NAME/*.o build/circuit.o build/version.o
+make -j16 BUILD=variants/build_$NAME LIB=variants/libp2v_$NAME.so EXTRA_HIPFLAGS="$EXTRA" variants/libp2v_$NAME.so

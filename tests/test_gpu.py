@@ -251,7 +251,7 @@ def test_gpu_n12_standard_batch_vs_oracle(p2v):
 @pytest.mark.parametrize("form", ["row", "quad", "lane"])
 @pytest.mark.parametrize("nb,mode,lk,pis", [(6, 1, 0, 4), (6, 0, 2, 0), (8, 1, 0, 19)])
 def test_gpu_transcript_forms_vs_oracle(p2v, form, nb, mode, lk, pis):
-    """The three transcript layouts (16, 4 lanes and 1 lane per proof; api.cpp picks them
+    """The three transcript layouts (16, 4 lanes and 1 lane per proof; api_run.cpp picks them
     by batch size, P2V_TRANSCRIPT forces any) give the oracle's challenges and statuses: real and
     degenerate circuits, lookups, 0 / 4 / 19 public inputs (19: a partial last PI block)."""
     gc = gen_circuit(nb, pis, lk, mode=mode)

@@ -31,7 +31,7 @@ def p2v():
 
 
 def kernels(vk, gates):
-    """The vanishing kernels a run of this circuit launches (csrc/api.cpp), from r and the classes
+    """The vanishing kernels a run of this circuit launches (csrc/api_run.cpp), from r and the classes
     its gates fall into."""
     sfx = "_r2" if vk.info.num_challenges == 2 else "_rn"
     out = ["k_vanish" + sfx]

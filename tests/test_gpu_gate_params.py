@@ -1,5 +1,5 @@
 """GPU tests (MI355X) of gate parameters other than the generator's one set per gate kind
-(csrc/vanish.h eval_gate, gate_coset, gate_random_access; the host plan of csrc/api.cpp: each
+(csrc/vanish.h eval_gate, gate_coset, gate_random_access; the host plan of csrc/api_workspace.cpp: each
 item's first alpha exponent, the coset part counts, the heaviest-first order), and of gate
 programs fed with edge values.
 

@@ -421,6 +421,26 @@ def test_source_hash_covers_the_library_sources(tmp_path):
     assert srchash.source_hash(str(tmp_path / "pkg")) != h
 
 
+def test_version_object_depends_on_what_the_source_hash_covers():
+    """The Makefile rebuilds version.o (the hash p2v_version() reports) from exactly the files
+    srchash.py hashes, so no file can change the hash check_build() demands without also
+    triggering the rebuild that satisfies it; the host units of the C-ABI are in both sets."""
+    import subprocess
+    import sys
+    pkg = os.path.join(ROOT, "plonky2-verifier_amd")
+    sys.path.insert(0, pkg)
+    import srchash
+    out = subprocess.run(["make", "-s", "-C", pkg, "print-version-deps"], check=True, capture_output=True, text=True).stdout
+    deps = [os.path.normpath(p) for p in out.split()]
+    want = [os.path.normpath(p) for p in srchash.source_files(pkg)]
+    assert sorted(deps) == sorted(want)
+    assert len(set(deps)) == len(deps)
+    units = [f for f in os.listdir(os.path.join(pkg, "csrc")) if f.startswith("api") and f.endswith(".cpp")]
+    assert "api.cpp" in units and len(units) > 1
+    for f in units + ["api_internal.hpp", "kernels.h"]:
+        assert os.path.join("csrc", f) in deps, f
+
+
 def test_c_abi_argument_contract():
     """The argument checks of the C ABI, through ctypes and without a device: a null handle or
     pointer is P2V_E_ARG with a message, before any device call (so before P2V_E_NODEVICE); an
