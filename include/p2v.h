@@ -496,7 +496,10 @@ int  p2v_verify_batch_devices(const p2v_circuit* c, const uint64_t* proofs, size
  *         transcript and the small-batch Merkle paths: 9 row (16 lanes per state), 10 quad
  *         (4 lanes)                                        (Hash/Poseidon.hs:42-46)
  *   op 11 (the retired pair form's permutation) is refused with P2V_E_ARG.
- * Inputs of ops 0-10 may be any u64 (values >= p are congruent, as the reference reads them).
+ *   op 22: out[12i..] = the leading merged unit of the throughput permutation on u = a[12i..], the
+ *         S-box outputs of full round 3: that round's MDS and partial rounds 4-5 as one unit, i.e.
+ *         the state entering round 6, canonical (Poseidon.hs:48-60)
+ * Inputs of ops 0-10 and 22 may be any u64 (values >= p are congruent, as the reference reads them).
  *
  * Ops 12-20: the F / F^2 arithmetic and the FRI query code of k_fri and the vanishing kernels,
  * each op the production function itself, one lane per item; a = n items of the stated words,

@@ -94,14 +94,14 @@ static int selftest_prog(int device, const uint64_t* a, const uint64_t* b, uint6
 int p2v_selftest(int device, int op, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n) {
   const bool needs_b = op == 0 || op == 3 || op == 4 || op == 6;
   // op 11 was the retired pair form's permutation; the ops keep their numbers
-  if (op < 0 || op > 21 || op == 11 || (n && (!a || !out || (needs_b && !b)))) return fail(P2V_E_ARG, "bad op / null argument");
+  if (op < 0 || op > 22 || op == 11 || (n && (!a || !out || (needs_b && !b)))) return fail(P2V_E_ARG, "bad op / null argument");
   if (op == 21) return selftest_prog(device, a, b, out, n);
   const int ndev = p2v_device_count();
   if (ndev == 0) return fail(P2V_E_NODEVICE, "no HIP device");
   if (device < 0 || device >= ndev) return fail(P2V_E_ARG, "bad device index");
-  if (op < 12 && n == 0) return P2V_OK;
+  if ((op < 12 || op == 22) && n == 0) return P2V_OK;
   HCK(hipSetDevice(device));
-  if (op >= 12) return selftest_field(op, a, b, out, n);
+  if (op >= 12 && op <= 20) return selftest_field(op, a, b, out, n);
   // words per item of a / b and of out
   const bool scalar = op == 0 || op == 3 || op == 5 || op == 6 || op == 7 || op == 8;
   const size_t w = scalar ? 1 : 12, wo = op == 6 ? 2 : w;
@@ -112,7 +112,7 @@ int p2v_selftest(int device, int op, const uint64_t* a, const uint64_t* b, uint6
   SCK(hipMemcpy(da.p, a, n * w * 8, hipMemcpyHostToDevice));
   if (needs_b) SCK(hipMemcpy(db.p, b, bw * 8, hipMemcpyHostToDevice));
   if (op >= 9) {
-    const int lanes = op == 9 ? 16 : 4;
+    const size_t lanes = op == 9 ? 16 : op == 10 ? 4 : 1;   // op 22: one lane per item
     hipLaunchKernelGGL(k_selftest_forms, dim3((unsigned)((n * lanes + 255) / 256)), dim3(256), 0, 0, op, (const uint64_t*)da.p,
                        (uint64_t*)dout.p, (int64_t)n);
   } else {

@@ -697,7 +697,24 @@ extern "C" __global__ void __launch_bounds__(256) k_selftest(int op, const uint6
 // r4): 9 the row form (lposeidon.h; 16 lanes per state), 10 the quad form (qposeidon.h, 4 lanes).
 // Every lane of a group takes part in the DPP moves, so lanes past n compute on a copy of state
 // n - 1 and store nothing.  a, out: n states of 12 words.
+// Op 22: the leading merged unit of the throughput form alone (poseidon.h PFTab, dv::pblock<3, true>),
+// one lane per item: a = the 12 S-box outputs u of full round 3 (any u64), out = the state entering
+// round 6, canonical.  u cannot be steered through a whole permutation, so the unit's row
+// reductions and their rare carry fix-ups are driven here.
 extern "C" __global__ void __launch_bounds__(256) k_selftest_forms(int op, const uint64_t* a, uint64_t* out, int64_t n) {
+  if (op == 22) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    uint64_t u[12], t[12];
+#pragma unroll
+    for (int k = 0; k < 12; k++) u[k] = a[12 * i + k];
+    p2::dv::pblock<3, true>(u, t, p2::c_pf.lead);
+#pragma unroll
+    for (int k = 0; k < 12; k++) out[12 * i + k] = gl::canon(t[k]);
+#endif
+    return;
+  }
   __shared__ TLdsAny T;
   tlds_fill_form(T, op == 9 ? 16 : 4);
   const int lanes = op == 9 ? 16 : 4;

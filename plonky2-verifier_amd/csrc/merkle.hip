@@ -71,18 +71,20 @@ __device__ __forceinline__ uint64_t cap_root(const DevCircuit& c, int t, uint32_
 
 // ---- lane form: one lane per path
 // One level of a path (Hash/Merkle.hs:27-42): even index compress(cur, sib), odd compress(sib, cur)
+// LEAD: permute_dev's (poseidon.h; false in k_merkle alone)
+template <bool LEAD = true>
 __device__ __forceinline__ void merkle_level(uint64_t (&cur)[4], const uint64_t (&sib)[4], bool odd) {
   uint64_t st[12];
 #pragma unroll
   for (int i = 0; i < 4; i++) { st[i] = odd ? sib[i] : cur[i]; st[4 + i] = odd ? cur[i] : sib[i]; st[8 + i] = 0; }
-  p2::permute_dev(st, true, 1);   // compress: words 8..11 enter as 0, only 0..3 are read
+  p2::permute_dev<true, LEAD>(st, true, 1);   // compress: words 8..11 enter as 0, only 0..3 are read
 #pragma unroll
   for (int i = 0; i < 4; i++) cur[i] = st[i];
 }
 // Levels [l0, l1) from node cur at index idx (both left at level l1), the siblings at poff.
 // node(l) runs between a level's sibling load and its compression (merkle_chain's check (B)).
 struct NoNode { __device__ __forceinline__ void operator()(int) const {} };
-template <class F = NoNode>
+template <class F = NoNode, bool LEAD = true>
 __device__ __forceinline__ void lane_climb(const DevCircuit& c, int64_t poff, int l0, int l1, int p, uint64_t (&cur)[4], uint32_t& idx, F node = F{}) {
   for (int l = l0; l < l1; l++) {
     uint64_t sib[4];
@@ -91,7 +93,7 @@ __device__ __forceinline__ void lane_climb(const DevCircuit& c, int64_t poff, in
 #pragma unroll
     for (int i = 0; i < 4; i++) sib[i] = ld(c, poff + 4 * l + i, p);
     node(l);
-    merkle_level(cur, sib, idx & 1u);
+    merkle_level<LEAD>(cur, sib, idx & 1u);
     idx >>= 1;
   }
 }
@@ -137,7 +139,7 @@ __device__ __forceinline__ bool path_ok(const DevCircuit& c, int t, int q, int p
   tree_path(c, t, q, p, depth, poff, idx);
   uint64_t cur[4];
   load_leafdig(c, t, q, p, cur);
-  lane_climb(c, poff, 0, depth, p, cur, idx);
+  lane_climb<NoNode, false>(c, poff, 0, depth, p, cur, idx);
   return cap_ok(c, t, idx, cur, p);
 }
 __device__ __forceinline__ void merkle_unit(const DevCircuit& c) {

@@ -222,31 +222,59 @@ __host__ __device__ constexpr PMD pm_d(int r, int D) {
     }
   return R;
 }
+// the table of one block of D partial rounds starting at round r
+__host__ __device__ constexpr PBlock pm_block(const PMAlg& A, int r, int D) {
+  PBlock B{};
+  const PMD dd = pm_d(r, D);
+  for (int k = 1; k < D; k++) { B.dlo[k - 1] = dd.d[k][0] & 0xFFFFFFFFull; B.dhi[k - 1] = dd.d[k][0] >> 32; }
+  for (int k = 2; k < D; k++) {
+    for (int j = 0; j < 12; j++) B.cf[k - 2][j] = (uint32_t)A.G[k][0][j];
+    for (int m = 2; m < k; m++) B.cf[k - 2][12 + m - 2] = (uint32_t)A.H[k][m][0];
+  }
+  for (int i = 0; i < 12; i++) {
+    for (int j = 0; j < 12; j++) B.cf[2 + i][j] = (uint32_t)A.G[D][i][j];
+    for (int m = 2; m < D; m++) B.cf[2 + i][12 + m - 2] = (uint32_t)A.H[D][m][i];
+    B.dlo[4 + i] = dd.d[D][i] & 0xFFFFFFFFull;
+    B.dhi[4 + i] = dd.d[D][i] >> 32;
+  }
+  return B;
+}
 __host__ __device__ constexpr PMTab make_pm() {
   PMTab T{};
   const PMAlg A = pm_alg();
   int r = 4;
   for (int b = 0; b < PM_NB; b++) {
-    const int D = PM_SCHED[b];
-    const PMD dd = pm_d(r, D);
-    PBlock& B = T.b[b];
-    for (int k = 1; k < D; k++) { B.dlo[k - 1] = dd.d[k][0] & 0xFFFFFFFFull; B.dhi[k - 1] = dd.d[k][0] >> 32; }
-    for (int k = 2; k < D; k++) {
-      for (int j = 0; j < 12; j++) B.cf[k - 2][j] = (uint32_t)A.G[k][0][j];
-      for (int m = 2; m < k; m++) B.cf[k - 2][12 + m - 2] = (uint32_t)A.H[k][m][0];
-    }
-    for (int i = 0; i < 12; i++) {
-      for (int j = 0; j < 12; j++) B.cf[2 + i][j] = (uint32_t)A.G[D][i][j];
-      for (int m = 2; m < D; m++) B.cf[2 + i][12 + m - 2] = (uint32_t)A.H[D][m][i];
-      B.dlo[4 + i] = dd.d[D][i] & 0xFFFFFFFFull;
-      B.dhi[4 + i] = dd.d[D][i] >> 32;
-    }
-    r += D;
+    T.b[b] = pm_block(A, r, PM_SCHED[b]);
+    r += PM_SCHED[b];
   }
+  return T;
+}
+// The throughput form (permute_dev) has a schedule of its own: full round 3's MDS is folded into
+// the first merged unit.  After round 3's S-boxes (outputs u) nothing nonlinear touches words
+// 1..11 of M u + rc[4] before the next materialisation, so with s'_0 = y1 = sbox((M u)_0 + rc[4][0])
+// and s'_j = (M u + rc[4])_j (j >= 1) the state after PF_LEAD partial rounds is
+//   G'_k u + G_k[:,0] y1 + sum_{m=2..k} H_k[:,m] y_m + d'_k,   k = PF_LEAD,
+//   G'_k = G_k[:,1:] M[1:,:],   d'_k = G_k[:,1:] rc[4][1:] + d_k (mod p),
+// and the S-box input of the unit's round k + 1 is row 0 of the same expression at level k.
+// G'_k = G_{k+1}, G_k[:,0] = H_{k+1}[:,2] and d'_k is d_{k+1} of a block starting at round 3
+// (whose d_1 = rc[4]): the unit is the block of PF_LEAD + 1 partial rounds starting at round 3
+// with its first S-box left out, because round 3 has already passed word 0 through its own.  It
+// has that block's bounds (depth 3: coefficients < 2^20.4, row sums < 2^23.9), and one
+// materialisation fewer covers rounds 3..25: (M3 + 2), 4, 4, 4, 4, 4 against M3, 4, 4, 4, 4, 4, 2.
+static constexpr int PF_LEAD = 2;   // partial rounds in the leading unit
+static constexpr int PF_NB = 5;     // blocks of 4 after it, from round 4 + PF_LEAD
+static_assert(PF_LEAD + 4 * PF_NB == 22, "the schedule must cover the 22 partial rounds");
+struct PFTab { PBlock lead; PBlock b[PF_NB]; };
+__host__ __device__ constexpr PFTab make_pf() {
+  PFTab T{};
+  const PMAlg A = pm_alg();
+  T.lead = pm_block(A, 3, PF_LEAD + 1);
+  for (int b = 0; b < PF_NB; b++) T.b[b] = pm_block(A, 4 + PF_LEAD + 4 * b, 4);
   return T;
 }
 #if defined(__HIPCC__)
 static __constant__ PMTab c_pm = make_pm();
+static __constant__ PFTab c_pf = make_pf();
 #endif
 
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -458,14 +486,14 @@ __device__ __forceinline__ void prow(const uint64_t* s, const uint64_t* yh, uint
     ah = madv((uint32_t)(yh[m] >> 32), cf[12 + m], ah);
   }
 }
-// D = 4 output rows I..11
-template <int I>
-__device__ __forceinline__ void pblock4_rows(const uint64_t* s, const uint64_t* y, uint64_t* t, const PBlock& B) {
+// output rows I..11 at depth D = 3 (row sums < 2^24) or 4
+template <int D, int I>
+__device__ __forceinline__ void pblock_rows(const uint64_t* s, const uint64_t* y, uint64_t* t, const PBlock& B) {
   if constexpr (I < 12) {
     uint64_t al, ah;
-    prow<mds_coeff(I, 0), 2>(s, y + 2, y[4], B.cf[2 + I], B.dlo[4 + I], B.dhi[4 + I], al, ah);
-    t[I] = reduce_w(al, ah);
-    pblock4_rows<I + 1>(s, y, t, B);
+    prow<mds_coeff(I, 0), D - 2>(s, y + 2, y[D], B.cf[2 + I], B.dlo[4 + I], B.dhi[4 + I], al, ah);
+    t[I] = D == 4 ? reduce_w(al, ah) : reduce_t(al, ah);
+    pblock_rows<D, I + 1>(s, y, t, B);
   }
 }
 // D = 2 output row before its (rare: ~2^-15) carry fix-up, as row_unfixed
@@ -496,29 +524,31 @@ __device__ __forceinline__ void pblock2_group(const uint64_t* s, uint64_t y2, ui
 }
 // D = 2 or 4 partial rounds: s = the state entering the block's first round (its constants included),
 // t = the state entering the round after the block.  s is clobbered.
-template <int D>
+// LEAD (D = 3): the leading unit of permute_dev's schedule (PFTab): s = the S-box outputs of full
+// round 3, whose own S-box of word 0 stands for the block's first; t = the state entering round 6.
+template <int D, bool LEAD = false>
 __device__ __forceinline__ void pblock(uint64_t* s, uint64_t* t, const PBlock& B) {
-  static_assert(D == 2 || D == 4, "PM_SCHED holds blocks of 4 and 2");
-  uint64_t y[D + 1];
-  s[0] = sbox_one(s[0]);   // y1, word 0 of s'
-  {   // chain row 1 (row 0 of M s' + d1): inline MDS entries
-    uint64_t al = madk_s<mds_coeff(0, 0)>((uint32_t)s[0], B.dlo[0]);
-    uint64_t ah = madk_s<mds_coeff(0, 0)>((uint32_t)(s[0] >> 32), B.dhi[0]);
-    mds_acc<0, 1>(s, al, ah);
-    y[2] = sbox_one(reduce_rows(al, ah));
-  }
-  if constexpr (D == 4) {
-    uint64_t al, ah;   // chain row 2: row sums < 2^16, the branch form of the fix-up
-    prow<mds_coeff(0, 0), 0>(s, nullptr, y[2], B.cf[0], B.dlo[1], B.dhi[1], al, ah);
-    y[3] = sbox_one(reduce_rows(al, ah));
-    // chain row 3: row sums < 2^24
-    prow<mds_coeff(0, 0), 1>(s, y + 2, y[3], B.cf[1], B.dlo[2], B.dhi[2], al, ah);
-    y[4] = sbox_one(reduce_t(al, ah));
-    pblock4_rows<0>(s, y, t, B);
-  } else {
+  static_assert(LEAD ? D == 3 : D == 2 || D == 4, "blocks of 4 and 2, and the leading unit at depth 3");
+  uint64_t y[D + 1], al, ah;
+  if constexpr (!LEAD) s[0] = sbox_one(s[0]);   // y1, word 0 of s'
+  // chain row 1 (row 0 of M s' + d1): inline MDS entries
+  al = madk_s<mds_coeff(0, 0)>((uint32_t)s[0], B.dlo[0]);
+  ah = madk_s<mds_coeff(0, 0)>((uint32_t)(s[0] >> 32), B.dhi[0]);
+  mds_acc<0, 1>(s, al, ah);
+  y[2] = sbox_one(reduce_rows(al, ah));
+  if constexpr (D == 2) {
     pblock2_group<0>(s, y[2], t, B);
     pblock2_group<4>(s, y[2], t, B);
     pblock2_group<8>(s, y[2], t, B);
+  } else {
+    // chain row 2: row sums < 2^16, the branch form of the fix-up
+    prow<mds_coeff(0, 0), 0>(s, nullptr, y[2], B.cf[0], B.dlo[1], B.dhi[1], al, ah);
+    y[3] = sbox_one(reduce_rows(al, ah));
+    if constexpr (D == 4) {   // chain row 3: row sums < 2^24
+      prow<mds_coeff(0, 0), 1>(s, y + 2, y[3], B.cf[1], B.dlo[2], B.dhi[2], al, ah);
+      y[4] = sbox_one(reduce_t(al, ah));
+    }
+    pblock_rows<D, 0>(s, y, t, B);
   }
 }
 }  // namespace dv
@@ -534,12 +564,15 @@ __device__ __forceinline__ void pblock(uint64_t* s, uint64_t* t, const PBlock& B
 //    constant (the compiler otherwise turns 2/16 into 64-bit shifts of zero-extended register
 //    pairs and pays a v_mov per pair);
 //  * rounds alternate between two register sets (s -> t -> s), so no copies are needed at
-//    loop edges; full rounds run as 4 pairs, the 22 partial rounds as merged blocks (PBlock,
-//    PM_SCHED).
+//    loop edges; the 22 partial rounds run as merged blocks (PBlock), the first of them with
+//    full round 3's MDS folded in (PFTab).
 // FOLD: compile the peeled zh round 0 (round0_zh) into this call site; false leaves it out where zh
 // is never set (the leaf sponge's second block of a trip: with both of its call sites folded,
 // k_phase1 spilled 8 B)
-template <bool FOLD = true>
+// LEAD: full round 3's MDS folded into the leading merged unit (PFTab); false keeps round 3 whole
+// and the blocks of PM_SCHED, for k_merkle alone: forced to 6 waves per SIMD it has 80 VGPRs and
+// took 20 B of scratch with the folded form (79 VGPRs and none without it)
+template <bool FOLD = true, bool LEAD = true>
 __device__ __forceinline__ void permute_dev(uint64_t s[12], bool zh = false, int gm = 7) {
   uint64_t t[12];
   // keep zh / gm run-time uniform values (uniform branches); as compile-time constants the
@@ -567,40 +600,68 @@ __device__ __forceinline__ void permute_dev(uint64_t s[12], bool zh = false, int
 #pragma unroll
     for (int i = 8; i < 12; i++) s[i] = add_nc(s[i], rc0[i]);
   }
+  uint64_t o[12];
+  if constexpr (LEAD) {
+    // Two full rounds per trip, s -> t -> s: (0, 1), (2, [3..25], 26), (27, 28); round 29 follows.
+    // Round 3 runs as its S-boxes only: its MDS is part of the leading merged unit (PFTab), so the
+    // linear section of rounds 3..25 is materialised 6 times, not 7, and starts from the register
+    // set round 2 wrote.
 #pragma unroll 1
-  for (int k = k0; k < 4; k++) {   // full-round pairs (0,1) (2,3) (26,27) (28,29)
-    const int r = k < 2 ? 2 * k : 22 + 2 * k;
-    dv::round_pp(s, t, r, zh && k == 0, 7);   // (k == 0 with zh: only when not peeled)
-    dv::round_pp(t, s, r + 1, false, k == 3 ? gm : 7);
-    if (k == 1) {
-      // blocks of 4, 4, 4, 4, 4, 2 merged partial rounds; each loop trip reads its own table
-      // copies, so the coefficient loads stay inside the loop (no SGPR spills)
+    for (int k = k0; k < 3; k++) {
+      dv::round_pp(s, t, k < 2 ? 2 * k : 23 + 2 * k, zh && k == 0, 7);   // (k == 0 with zh: only when not peeled)
+      if (k == 1) {
+        dv::sbox_range<0, 12>(t);
+        // the leading unit (round 3's MDS + 2 partial rounds), then blocks of 4, 4, 4, 4, 4; each
+        // loop trip reads its own table copies, so the coefficient loads stay inside the loop (no
+        // SGPR spills)
+        dv::pblock<3, true>(t, s, c_pf.lead);
 #pragma unroll 1
-      for (int b = 0; b < 4; b += 2) {
-        dv::pblock<4>(s, t, c_pm.b[b]);
-        dv::pblock<4>(t, s, c_pm.b[b + 1]);
+        for (int b = 0; b < 4; b += 2) {
+          dv::pblock<4>(s, t, c_pf.b[b]);
+          dv::pblock<4>(t, s, c_pf.b[b + 1]);
+        }
+        dv::pblock<4>(s, t, c_pf.b[4]);
       }
-      dv::pblock<4>(s, t, c_pm.b[4]);
-      dv::pblock<2>(t, s, c_pm.b[5]);
+      dv::round_pp(t, s, k == 0 ? 1 : 24 + 2 * k, false, 7);
+    }
+    // round 29 into an array of its own, which the canonicalisation below moves to s: the groups
+    // it does not form stay undefined, where t's stale words would stay live through the round
+    dv::round_pp(s, o, 29, false, gm);
+  } else {
+#pragma unroll 1
+    for (int k = k0; k < 4; k++) {   // full-round pairs (0,1) (2,3) (26,27) (28,29)
+      const int r = k < 2 ? 2 * k : 22 + 2 * k;
+      dv::round_pp(s, t, r, zh && k == 0, 7);   // (k == 0 with zh: only when not peeled)
+      dv::round_pp(t, s, r + 1, false, k == 3 ? gm : 7);
+      if (k == 1) {   // blocks of 4, 4, 4, 4, 4, 2 merged partial rounds (PM_SCHED)
+#pragma unroll 1
+        for (int b = 0; b < 4; b += 2) {
+          dv::pblock<4>(s, t, c_pm.b[b]);
+          dv::pblock<4>(t, s, c_pm.b[b + 1]);
+        }
+        dv::pblock<4>(s, t, c_pm.b[4]);
+        dv::pblock<2>(t, s, c_pm.b[5]);
+      }
     }
   }
+  const uint64_t* e = LEAD ? o : s;
   // canonical outputs for the groups the caller reads (the others are undefined: their last MDS
   // rows were not formed); a compression's 8 unread words no longer pay ~5 VALU each (round 6)
   if (gm & 1) {
 #pragma unroll
-    for (int i = 0; i < 4; i++) s[i] = gl::canon(s[i]);
+    for (int i = 0; i < 4; i++) s[i] = gl::canon(e[i]);
   }
   if (gm & 2) {
 #pragma unroll
-    for (int i = 4; i < 8; i++) s[i] = gl::canon(s[i]);
+    for (int i = 4; i < 8; i++) s[i] = gl::canon(e[i]);
   }
   if (gm & 4) {
 #pragma unroll
-    for (int i = 8; i < 12; i++) s[i] = gl::canon(s[i]);
+    for (int i = 8; i < 12; i++) s[i] = gl::canon(e[i]);
   }
 }
 #elif defined(__HIPCC__)
-template <bool FOLD = true>
+template <bool FOLD = true, bool LEAD = true>
 __device__ void permute_dev(uint64_t s[12], bool zh = false, int gm = 7);   // device-only
 namespace dv { template <uint32_t C> __device__ uint64_t madk(uint32_t a, uint64_t acc); }
 #endif

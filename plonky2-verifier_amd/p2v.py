@@ -840,7 +840,9 @@ def device_selftest(op: int, a: np.ndarray, b: Optional[np.ndarray] = None, devi
     op 6 the grouped pair (a[i], b[i]) -> out [n, 2]) and the latency forms of the permutation
     (ops 9-10: row, quad) on `device`.  Ops 12-20: the F / F^2 arithmetic and the FRI query
     code (a = [n, item words], b = the op's shared words, out = [n, result words]; see p2v.h).
-    Op 21: the gate-program interpreter, b = [nwires, nconsts] + GateProgram.words()."""
+    Op 21: the gate-program interpreter, b = [nwires, nconsts] + GateProgram.words().
+    Op 22: the throughput permutation's leading merged unit (a = [n, 12] S-box outputs of round 3,
+    out = the state entering round 6, canonical)."""
     a = np.ascontiguousarray(a, dtype=np.uint64)
     n = a.shape[0]
     if op == 21:   # b = [nwires, nconsts, program words]; out: 2 words per COMMIT of the program
