@@ -221,6 +221,50 @@ int  p2v_vkey_from_json(const p2v_circuit* c, const char* vkey_json, size_t len,
 int  p2v_circuit_with_keys(const p2v_circuit* base, const uint64_t* key_words, size_t nkeys, p2v_circuit** out);
 int  p2v_circuit_num_keys(const p2v_circuit* c);
 
+/* ---- self-keyed circuits: each proof's key from its own public inputs -------------------
+ * plonky2 has a convention for a proof to say which verifier key it belongs to: a circuit built
+ * with add_verifier_data_public_inputs() (cyclic recursion, conditionally_verify_cyclic_proof, the
+ * aggregation and block circuits of recursion trees) ends its public inputs with its own
+ * VerifierOnlyCircuitData, and plonky2's verifier checks that tail
+ * (check_cyclic_proof_verifier_data, via VerifierOnlyCircuitData::from_slice).  The tail is the
+ * last 4 + 4 * cap_len public inputs:
+ *     public_inputs = [ ..., circuit_digest (4), cap[0] (4), ..., cap[cap_len - 1] (4) ]
+ * -- the digest FIRST, unlike the key encoding above (cap digests, then the digest).
+ * This is plonky2's convention, NOT the reference's: the reference has no such check, so like the
+ * P2V_EXT_* conventions it is opt-in and no entry point applies it to a handle that was not marked.
+ *
+ * A handle marked self-keyed (p2v_circuit_self_keyed) resolves, in every entry point that takes no
+ * key ids -- p2v_verifier_run, p2v_verifier_run_keyed with key_ids == NULL, p2v_verifier_run_json,
+ * p2v_verifier_run_bytes, p2v_verify_batch, p2v_verify_batch_keyed with NULL, p2v_verify_batch_bytes,
+ * p2v_verify_batch_devices -- each proof's id on the device (keys.hip k_key_resolve: the tail,
+ * reduced mod p, looked up in a hash table over the handle's keys) and verifies the proof against
+ * that key, as p2v_verifier_run_keyed with those ids would: no host round trip, nothing allocated
+ * per run.  Explicit key_ids OVERRIDE the resolution (the tail is then not read at all).  A proof
+ * whose tail equals no key of the table has the id P2V_KEY_NONE and gets the status
+ * P2V_ERR_CIRCUIT and an unspecified trace row, as any id >= p2v_circuit_num_keys does; it is
+ * never verified against the cap it declares.  Of equal keys in the table the lowest index is the
+ * id.  A one-key handle may be marked: it then enforces plonky2's cyclic check (every proof must
+ * name key 0).  Known openings: a self-keyed run is a keyed run, so it uses the per-key rows where
+ * a run with explicit ids would.
+ *   p2v_circuit_find_key   the lowest index of the key equal to key_words (key encoding, any u64,
+ *                          reduced mod p) in the handle's table; -1: none; P2V_E_ARG (-4) for a
+ *                          null argument -- the one function here whose -1 is not an error code
+ *   p2v_key_from_public_inputs   the tail of pis[0 .. npis) rearranged into the key encoding
+ *                          (key_words: 4 * cap_len + 4 words, copied as given); P2V_E_SHAPE when
+ *                          npis < 4 + 4 * cap_len
+ *   p2v_circuit_self_keyed a new handle (free with p2v_circuit_free) with base's key table,
+ *                          programs and `ext`, marked; P2V_E_CIRCUIT when the circuit's
+ *                          num_public_inputs < 4 + 4 * cap_len.  p2v_circuit_with_keys and
+ *                          p2v_circuit_shape_variant keep the mark; a shape variant with fewer
+ *                          public inputs than a key is still made, and every proof on it
+ *                          resolves to P2V_KEY_NONE
+ *   p2v_circuit_is_self_keyed   1 / 0 (< 0: P2V_E_ARG) */
+#define P2V_KEY_NONE 0xFFFFFFFFu
+int  p2v_circuit_find_key(const p2v_circuit* c, const uint64_t* key_words);
+int  p2v_key_from_public_inputs(const p2v_circuit* c, const uint64_t* pis, size_t npis, uint64_t* key_words);
+int  p2v_circuit_self_keyed(const p2v_circuit* base, p2v_circuit** out);
+int  p2v_circuit_is_self_keyed(const p2v_circuit* c);
+
 /* ---- gate programs: constraints of gates the library does not know (host-only) ----------
  * The reference knows 16 gate kinds; any other string of common.gates is an UnknownGate and the
  * circuit is refused (Gate/Constraints.hs:108; P2V_E_CIRCUIT here).  Its own gates are
@@ -391,7 +435,8 @@ int  p2v_circuit_known_key_rows(const p2v_circuit* c, int device, uint32_t key, 
  * copied through a staging buffer made by p2v_verifier_create: the run allocates nothing and
  * stays capturable).  Every flag keeps its meaning; under P2V_FLAG_LOOKAHEAD the ids are, like
  * the proofs, complete in device memory when the call is made.  key_ids == NULL is exactly
- * p2v_verifier_run (every proof against key 0).  A proof whose id is >= p2v_circuit_num_keys
+ * p2v_verifier_run (every proof against key 0; on a self-keyed handle: against the key its public
+ * inputs name, "self-keyed circuits" above).  A proof whose id is >= p2v_circuit_num_keys
  * gets the status P2V_ERR_CIRCUIT (host and device ids alike; nothing is read out of bounds) and
  * an unspecified trace row.  The key enters the transcript's first absorb and the cap comparison
  * of the constants/sigmas tree only (DESIGN.md "Key tables"), so a keyed batch costs what an
@@ -400,6 +445,18 @@ int  p2v_circuit_known_key_rows(const p2v_circuit* c, int device, uint32_t key, 
  * CommonCircuitData (Plonk/Verifier.hs:56-65, Types.hs:220-240). */
 int  p2v_verifier_run_keyed(p2v_verifier* v, const uint64_t* proofs, const uint32_t* key_ids, size_t n,
                             int8_t* results, uint64_t* trace, void* stream, uint32_t flags);
+
+/* The resolution of a self-keyed run alone ("self-keyed circuits" above), on any handle, marked
+ * or not: key_ids[i] = the index of the key that proof i's public inputs end with, or
+ * P2V_KEY_NONE.  Flags: P2V_FLAG_INPUT_DEVICE / P2V_FLAG_INPUT_TILED for the proofs as in
+ * p2v_verifier_run, P2V_FLAG_RESULT_DEVICE (key_ids is device memory, n u32) and, with it,
+ * P2V_FLAG_NO_SYNC.  Host proofs go through the workspace's input staging buffer and host ids
+ * through the staging buffer of host-given key ids, the two that a p2v_verifier_run_keyed from host
+ * memory uses: order the call with the workspace's other calls on one stream, as such a run.  It
+ * touches neither id buffer of the P2V_FLAG_LOOKAHEAD runs, so with device proofs it may be
+ * enqueued while lookahead runs of the same workspace are in flight. */
+int  p2v_verifier_resolve_keys(p2v_verifier* v, const uint64_t* proofs, size_t n, uint32_t* key_ids,
+                               void* stream, uint32_t flags);
 
 /* Stagger two or more workspaces that run back-to-back batches on their own streams: after
  * p2v_verifier_chain(v, prev), every later run of v starts its phase 1 (transcript + leaf

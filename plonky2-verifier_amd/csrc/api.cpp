@@ -15,6 +15,31 @@ p2v_circuit::~p2v_circuit() {
   for (auto& k : known) { (void)hipSetDevice(k->device); k.reset(); }
 }
 
+// Keys in ascending index order, a key equal to an earlier one skipped: the lowest index wins.
+const std::vector<uint32_t>& p2v_circuit::key_lookup() const {
+  std::call_once(key_tab_once, [&] {
+    const size_t nk = c.num_keys();
+    const int kw = c.key_words();
+    size_t size = 2;
+    while (size < 2 * nk) size <<= 1;
+    key_tab.assign(size, 0);
+    const uint32_t mask = (uint32_t)size - 1;
+    for (size_t k = 0; k < nk; k++) {
+      uint64_t h = 0;
+      for (int i = 0; i < kw; i++) h = p2v_key_hash(h, c.key_word(k, i));
+      uint32_t slot = (uint32_t)h & mask;
+      for (; key_tab[slot]; slot = (slot + 1) & mask) {
+        const size_t e = key_tab[slot] - 1;
+        int i = 0;
+        while (i < kw && c.key_word(e, i) == c.key_word(k, i)) i++;
+        if (i == kw) break;
+      }
+      if (!key_tab[slot]) key_tab[slot] = (uint32_t)k + 1;
+    }
+  });
+  return key_tab;
+}
+
 extern "C" {
 
 const char* p2v_last_error_message(void) { return g_err.c_str(); }
@@ -203,6 +228,51 @@ int p2v_circuit_with_keys(const p2v_circuit* base, const uint64_t* key_words, si
 int p2v_circuit_num_keys(const p2v_circuit* pc) {
   if (!pc) return fail(P2V_E_ARG, "null argument");
   return (int)pc->c.num_keys();
+}
+
+int p2v_circuit_find_key(const p2v_circuit* pc, const uint64_t* key_words) {
+  if (!pc || !key_words) return fail(P2V_E_ARG, "null argument");
+  const Circuit& C = pc->c;
+  const int kw = C.key_words();
+  const std::vector<uint32_t>& tab = pc->key_lookup();
+  const uint32_t mask = (uint32_t)tab.size() - 1;
+  uint64_t h = 0;
+  for (int i = 0; i < kw; i++) h = p2v_key_hash(h, key_words[i] % gl::P);
+  uint32_t slot = (uint32_t)h & mask;
+  for (size_t probes = 0; probes < tab.size() && tab[slot]; probes++, slot = (slot + 1) & mask) {
+    const size_t k = tab[slot] - 1;
+    int i = 0;
+    while (i < kw && C.key_word(k, i) == key_words[i] % gl::P) i++;
+    if (i == kw) return (int)k;
+  }
+  return -1;
+}
+
+int p2v_key_from_public_inputs(const p2v_circuit* pc, const uint64_t* pis, size_t npis, uint64_t* key_words) {
+  if (!pc || (!pis && npis) || !key_words) return fail(P2V_E_ARG, "null argument");
+  const int kw = pc->c.key_words(), cap_len = pc->c.cap_len;
+  if (npis < (size_t)kw) return fail(P2V_E_SHAPE, "public inputs shorter than a verifier key (4 + 4 * cap_len words)");
+  const uint64_t* tail = pis + (npis - (size_t)kw);
+  for (int i = 0; i < kw; i++) key_words[i] = tail[p2v_key_tail_word(i, cap_len)];
+  return P2V_OK;
+}
+
+int p2v_circuit_self_keyed(const p2v_circuit* base, p2v_circuit** out) {
+  if (!base || !out) return fail(P2V_E_ARG, "null argument");
+  *out = nullptr;
+  if (base->c.num_pis < base->c.key_words())
+    return fail(P2V_E_CIRCUIT, "p2v_circuit_self_keyed: the circuit's public inputs are shorter than a verifier key");
+  return guarded(P2V_E_ARG, [&] {
+    auto v = std::make_unique<p2v_circuit>();
+    v->c = base->c;
+    v->c.self_keyed = true;
+    *out = v.release();
+  });
+}
+
+int p2v_circuit_is_self_keyed(const p2v_circuit* pc) {
+  if (!pc) return fail(P2V_E_ARG, "null argument");
+  return pc->c.self_keyed ? 1 : 0;
 }
 
 int p2v_pack_proofs_json(const p2v_circuit* pc, const char* const* jsons, const size_t* lens, size_t n, uint64_t* dst,

@@ -114,6 +114,11 @@ struct p2v_circuit {
   mutable std::vector<HostPipe*> pool;   // idle and busy pipes of every device
   mutable std::mutex known_mu;
   mutable std::vector<std::unique_ptr<KnownTable>> known;   // one per device, made by the first workspace that wants it
+  // the key lookup table (dev.h DevCircuit::key_tab), built by the first call that needs it
+  // (p2v_circuit_find_key, p2v_verifier_create); the key table never changes after construction
+  mutable std::once_flag key_tab_once;
+  mutable std::vector<uint32_t> key_tab;
+  const std::vector<uint32_t>& key_lookup() const;   // api.cpp
   ~p2v_circuit();
 };
 
@@ -173,6 +178,9 @@ struct p2v_verifier {
   Stream ts;                        // the lookahead transcript's
   Stream side3;                     // latency mode: the coset / misc vanishing kernels beside the Poseidon parts
   DevBuf kid;                       // staging for key ids given in host memory (p2v_verifier_run_keyed): Bmax u32
+  DevBuf kres[2];                   // the ids k_key_resolve writes (self-keyed runs), Bmax u32 each: [la_slot], as the
+                                    // challenge buffers, so two lookahead runs in flight keep their own
+  DevBuf t_ktab;                    // DevCircuit::key_tab
   DevBuf in, chal, chal2, leafdig, mk, fbits, qvals, van, vparts, lutre, lutpart, res, trace;
   DevBuf m_plan, m_fol, m_chain, m_count, m_fix, m_badq, m_node;   // shared-node Merkle paths (dev.h mcse)
   DevBuf k_miss, k_missn;           // known openings: this workspace's miss list and its length

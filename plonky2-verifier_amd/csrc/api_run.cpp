@@ -43,7 +43,9 @@ int p2v_verifier_run(p2v_verifier* v, const uint64_t* proofs, size_t n, int8_t* 
   return p2v_verifier_run_keyed(v, proofs, nullptr, n, results, trace, stream_, flags);
 }
 
-// key_ids == nullptr: every proof against key 0, the kernels' unkeyed path (d.key_id stays null)
+// key_ids == nullptr: every proof against key 0, the kernels' unkeyed path (d.key_id stays null);
+// on a self-keyed handle instead the ids k_key_resolve reads from the proofs (keys.hip), and the
+// run is a keyed run from there on
 int p2v_verifier_run_keyed(p2v_verifier* v, const uint64_t* proofs, const uint32_t* key_ids, size_t n, int8_t* results,
                            uint64_t* trace, void* stream_, uint32_t flags) {
   if (!v || (!proofs && n) || !results) return fail(P2V_E_ARG, "null argument");
@@ -71,6 +73,8 @@ int p2v_verifier_run_keyed(p2v_verifier* v, const uint64_t* proofs, const uint32
     HCK(hipMemcpyAsync(v->kid.p, key_ids, n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
     d.key_id = (const uint32_t*)v->kid.p;
   }
+  const bool resolve = !key_ids && C.self_keyed;   // d.key_id: the id buffer of this run's parity, set where it is launched
+  const bool has_ids = key_ids || resolve;
   int8_t* dres = (flags & P2V_FLAG_RESULT_DEVICE) ? results : (int8_t*)v->res.p;
   uint64_t* dtrace = nullptr;
   if (trace) dtrace = (flags & P2V_FLAG_RESULT_DEVICE) ? trace : (uint64_t*)v->trace.p;
@@ -105,7 +109,7 @@ int p2v_verifier_run_keyed(p2v_verifier* v, const uint64_t* proofs, const uint32
   // kernels index it by the id clamped to nkeys - 1); a keyed run on a one-key handle keeps the
   // launch sequence it had.
   const bool lat = d.n <= v->lat_max_batch;
-  const bool key_rows = !key_ids || (d.nkeys > 1 && v->known && v->known->kkeys == d.nkeys);
+  const bool key_rows = !has_ids || (d.nkeys > 1 && v->known && v->known->kkeys == d.nkeys);
   if (v->known && key_rows && !lat && d.mcse) {
     d.kmode = v->known_mode; d.kskip = 1;
     int k = 0;
@@ -130,6 +134,12 @@ int p2v_verifier_run_keyed(p2v_verifier* v, const uint64_t* proofs, const uint32
     la_slot = (int)(v->la_seq++ & 1u);
     d.chal = (uint64_t*)(la_slot ? v->chal2.p : v->chal.p);
     HCK(hipStreamWaitEvent(v->ts, v->chal_free[la_slot], 0));
+    if (resolve) {   // ahead of the transcript, its first reader; the run that last read this id buffer is the
+                     // one that last read the challenge buffer (k_leaf on st reads no key)
+      d.key_id = (const uint32_t*)v->kres[la_slot].p;
+      k_key_resolve<<<d.B / 256 + (d.B % 256 != 0), 256, 0, v->ts>>>(d, (uint32_t*)v->kres[la_slot].p);
+      DBG("k_key_resolve", v->ts);
+    }
     T0(SLOT_TRANSCRIPT, v->ts);
     launch_transcript(d, tl, nt_blocks, v->ts);
     DBG("k_transcript", v->ts);
@@ -143,6 +153,11 @@ int p2v_verifier_run_keyed(p2v_verifier* v, const uint64_t* proofs, const uint32
     HCK(hipEventRecord(v->dep_p1, st));                     // the side kernels read the challenges
     HCK(hipStreamWaitEvent(sd, v->dep_p1, 0));
   } else {
+    if (resolve) {
+      d.key_id = (const uint32_t*)v->kres[0].p;
+      k_key_resolve<<<d.B / 256 + (d.B % 256 != 0), 256, 0, st>>>(d, (uint32_t*)v->kres[0].p);
+      DBG("k_key_resolve", st);
+    }
     T0(SLOT_PHASE1, st);
     launch_phase1(d, tl, nt_blocks, (leaf_units + 3) / 4, st);
     DBG("k_phase1", st);
@@ -287,6 +302,41 @@ int p2v_verifier_run_keyed(p2v_verifier* v, const uint64_t* proofs, const uint32
       (void)hipGetLastError();   // a failed timing query must not surface as the next call's error
     }
   }
+  return P2V_OK;
+}
+
+// the resolution of a self-keyed run alone, on any handle
+int p2v_verifier_resolve_keys(p2v_verifier* v, const uint64_t* proofs, size_t n, uint32_t* key_ids, void* stream_, uint32_t flags) {
+  if (!v || (!proofs && n) || (!key_ids && n)) return fail(P2V_E_ARG, "null argument");
+  if (n > v->max_batch) return fail(P2V_E_ARG, "batch larger than max_batch");
+  if (n == 0) return P2V_OK;
+  HCK(hipSetDevice(v->device));
+  hipStream_t st = (hipStream_t)stream_;
+  DevCircuit d = v->dc;
+  d.n = (int)n;
+  d.tiled = (flags & P2V_FLAG_INPUT_TILED) ? 1 : 0;
+  d.wstride = d.tiled ? 64 : 1;
+  d.B = (int)((n + 63) / 64 * 64);
+  d.soa = proofs;
+  if (!(flags & P2V_FLAG_INPUT_DEVICE)) {
+    const size_t words = (size_t)v->circ->c.L.words;
+    HCK(input_buf(v));
+    HCK(hipMemcpyAsync(v->in.p, proofs, (d.tiled ? p2v_tiled_words(n, words) : words * n) * 8, hipMemcpyHostToDevice, st));
+    d.soa = (const uint64_t*)v->in.p;
+  }
+  const bool to_device = flags & P2V_FLAG_RESULT_DEVICE;
+  // host ids stage through `kid`, as host-given ids do: only stream-ordered runs touch it, never a
+  // lookahead run's resolver on v->ts (which writes kres[la_slot])
+  uint32_t* dids = to_device ? key_ids : (uint32_t*)v->kid.p;
+  k_key_resolve<<<d.B / 256 + (d.B % 256 != 0), 256, 0, st>>>(d, dids);
+  if (v->debug_sync) {
+    fprintf(stderr, "p2v: launched k_key_resolve\n"); fflush(stderr);
+    HCK(hipStreamSynchronize(st)); HCK(hipGetLastError());
+    fprintf(stderr, "p2v: finished k_key_resolve\n"); fflush(stderr);
+  }
+  HCK(hipGetLastError());
+  if (!to_device) HCK(hipMemcpyAsync(key_ids, dids, n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  if (!(flags & P2V_FLAG_NO_SYNC) || !to_device) HCK(hipStreamSynchronize(st));
   return P2V_OK;
 }
 

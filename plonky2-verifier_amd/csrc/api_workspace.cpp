@@ -274,8 +274,12 @@ int p2v_verifier_create(const p2v_circuit* pc, int device, size_t max_batch, p2v
     ACK(upload(v->t_cs, keys, d.keys));
     d.cs_cap = d.keys;
     d.nkeys = (int32_t)C.num_keys();
+    const std::vector<uint32_t>& tab = pc->key_lookup();   // the lookup over them (keys.hip k_key_resolve)
+    ACK(upload(v->t_ktab, tab, d.key_tab));
+    d.key_tab_mask = (uint32_t)tab.size() - 1;
   }
   ACK(v->kid.alloc(v->Bmax * sizeof(uint32_t)));
+  for (DevBuf& b : v->kres) ACK(b.alloc(v->Bmax * sizeof(uint32_t)));
   ACK(upload(v->t_kis, C.k_is, d.k_is));
   ACK(upload(v->t_gkind, t.gkind, d.gate_kind)); ACK(upload(v->t_gpar, t.gpar, d.gate_par)); ACK(upload(v->t_ggrp, t.ggrp, d.gate_grp));
   ACK(upload(v->t_gwoff, t.gwoff, d.gate_woff)); ACK(upload(v->t_w, t.wts, d.weights)); ACK(upload(v->t_gs, t.gs, d.grp_start)); ACK(upload(v->t_ge, t.ge, d.grp_end));

@@ -95,6 +95,14 @@ struct Circuit {
   std::vector<uint64_t> extra_keys;
   int key_words() const { return 4 * cap_len + 4; }
   size_t num_keys() const { return 1 + extra_keys.size() / (size_t)key_words(); }
+  // word i of key k in the key encoding
+  uint64_t key_word(size_t k, int i) const {
+    if (k) return extra_keys[(k - 1) * (size_t)key_words() + i];
+    return i < 4 * cap_len ? cs_cap[i] : digest[i - 4 * cap_len];
+  }
+  // self-keyed handle (p2v_circuit_self_keyed): runs without ids resolve each proof's key from the
+  // tail of its public inputs (include/p2v.h "self-keyed circuits"); kept by the derived handles
+  bool self_keyed = false;
   int final_len_override = -1;              // shape variant (circuit_shape_variant): final_poly length
   // derived
   int cap_len = 0, final_len = 0;

@@ -124,6 +124,12 @@ struct DevCircuit {
   const uint64_t* gprog;
   const int64_t* gate_poff;        // [n_gates]
   int64_t prog_pih;                // p2v_selftest op 21: the item word of the hash words; -1: the challenge buffer
+  // Key lookup (keys.hip k_key_resolve, include/p2v.h "self-keyed circuits"): open addressing over
+  // key_tab_mask + 1 u32 slots (a power of two >= 2 nkeys), a slot holding key index + 1 or 0 (empty),
+  // start slot p2v_key_hash of the key's words & key_tab_mask, linear probing; of equal keys only the
+  // lowest index is in the table
+  const uint32_t* key_tab;
+  uint32_t key_tab_mask;
 };
 #define P2V_PROG_SLOTS 32          // LDS slots of the interpreter = P2V_GATE_PROGRAM_MAX_LIVE (include/p2v.h)
 #define P2V_KNOWN_EMPTY 0u
@@ -176,6 +182,19 @@ static inline P2V_HD int64_t p2v_coset_parts(int bits, int64_t degree, int64_t n
   return nint + 1 < nch ? nint + 1 : nch;
 }
 static inline P2V_HD int64_t p2v_coset_part_first_term(int64_t part) { return part == 0 ? 0 : 2 + 4 * part; }
+
+// The key lookup's hash (DevCircuit::key_tab), one word at a time: h = 0, then every canonical
+// (< p) word of the key in the key encoding's order, cap digests first.  All 4 cap_len + 4 words
+// enter, so keys that share their digest or their cap spread over the table; the multiply carries
+// a word's bits upward and the fold brings them back down to the bits the mask keeps.  The host's
+// table (api.cpp p2v_circuit::key_lookup), p2v_circuit_find_key and k_key_resolve all call this
+// one function.
+static inline P2V_HD uint64_t p2v_key_hash(uint64_t h, uint64_t word) {
+  h = (h ^ word) * 0x9E3779B97F4A7C15ull;
+  return h ^ (h >> 32);
+}
+// word i of the key encoding within the public inputs' tail [circuit_digest | cap] (wave-uniform)
+static inline P2V_HD int p2v_key_tail_word(int i, int cap_len) { return i < 4 * cap_len ? 4 + i : i - 4 * cap_len; }
 
 // challenge buffer offsets (match the P2V_TRACE layout prefix in include/p2v.h)
 #define CH_PI(c) 0

@@ -716,13 +716,16 @@ void batch_inv_base(std::vector<u64>& v) {   // Montgomery's trick over F (no ze
 // A real witness and the prover's first three rounds (Plonky2's order: wires, then Z/partial
 // products after beta/gamma, then the quotient after alpha), reproducing the verifier's
 // transcript (Challenge/Verifier.hs:58-92).
-Witness* make_witness_real(const Circuit& C, u64 seed) {
+// tail / ntail: the last ntail public inputs, written over the drawn ones (a circuit naming its
+// own verifier key, plonky2's add_verifier_data_public_inputs); the draws after them are unchanged
+Witness* make_witness_real(const Circuit& C, u64 seed, const u64* tail = nullptr, int ntail = 0) {
   auto* W = new Witness();
   Rng rg(seed * 1000003 + 11);
   make_salts(C, W, seed);
   const int N = C.N, NW = C.num_wires, NR = C.num_routed, NK = C.num_gate_consts, r = C.r, n = C.degree_bits;
   W->pis.resize(C.num_pis);
   for (auto& x : W->pis) x = rg.field();
+  for (int i = 0; i < ntail; i++) W->pis[W->pis.size() - ntail + i] = tail[i] % gl::P;
   u64 pih[4] = {0, 0, 0, 0};
   if (!W->pis.empty()) sponge(W->pis.data(), W->pis.size(), pih);
   // ---- lookups: per block the looked-up table entries (witness-random, the last LU row padded
@@ -1335,6 +1338,15 @@ void* p2v_gen_witness_new(void* c, uint64_t seed) {
   try {
     const Circuit& C = *(Circuit*)c;
     return C.real ? make_witness_real(C, seed) : make_witness(C, seed);
+  } catch (std::exception& e) { g_err = e.what(); return nullptr; }
+}
+// p2v_gen_witness_new of a real-mode circuit with its last ntail public inputs set to `tail`
+void* p2v_gen_witness_new_pis(void* c, uint64_t seed, const uint64_t* tail, int ntail) {
+  try {
+    const Circuit& C = *(Circuit*)c;
+    if (!C.real) { g_err = "p2v_gen_witness_new_pis: real modes only"; return nullptr; }
+    if (ntail < 0 || ntail > C.num_pis || (ntail && !tail)) { g_err = "p2v_gen_witness_new_pis: bad tail"; return nullptr; }
+    return make_witness_real(C, seed, tail, ntail);
   } catch (std::exception& e) { g_err = e.what(); return nullptr; }
 }
 void p2v_gen_witness_free(void* w) { delete (Witness*)w; }

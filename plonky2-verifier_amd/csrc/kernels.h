@@ -46,6 +46,8 @@ extern "C" __global__ void k_vanish_prog_rn(DevCircuit);
 extern "C" __global__ void k_selftest_prog(DevCircuit, uint64_t*, int);
 extern "C" __global__ void k_lut(DevCircuit);
 extern "C" __global__ void k_vanish_final(DevCircuit);
+// keys.hip
+extern "C" __global__ void k_key_resolve(DevCircuit, uint32_t*);
 // util.hip
 extern "C" __global__ void k_count_mismatches(const int8_t*, const int8_t*, int64_t, unsigned long long*);
 extern "C" __global__ void k_clock_probe(unsigned long long*);

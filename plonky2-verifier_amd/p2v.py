@@ -68,6 +68,7 @@ FLAG_UNIT_FILTERS = 8   # parity mode (tests only): every gate filter / lookup s
 FLAG_INPUT_TILED = 16   # the batch in 64-proof tiles [n/64][words][64] (tile_proofs)
 FLAG_LOOKAHEAD = 32     # the device batch is complete at the call: its transcript may run ahead (include/p2v.h)
 SHAPE_LIMIT = 1 << 20   # public inputs / final-polynomial coefficients a shape variant may hold (include/p2v.h)
+KEY_NONE = 0xFFFFFFFF     # P2V_KEY_NONE: the id of a proof whose public inputs name no key of the table
 SHAPE_VARIANTS_KEPT = 8   # shape variants a circuit keeps (least recently used evicted)
 
 
@@ -157,6 +158,11 @@ def lib() -> ctypes.CDLL:
     L.p2v_circuit_known_key_rows.argtypes = [vp, ctypes.c_int, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint64)]
     L.p2v_verifier_run_keyed.argtypes = [vp, u64p, vp, sz, i8p, u64p, vp, ctypes.c_uint32]
     L.p2v_verify_batch_keyed.argtypes = [vp, u64p, vp, sz, i8p, ctypes.c_int]
+    L.p2v_circuit_find_key.argtypes = [vp, u64p]
+    L.p2v_key_from_public_inputs.argtypes = [vp, u64p, sz, u64p]
+    L.p2v_circuit_self_keyed.argtypes = [vp, ctypes.POINTER(vp)]
+    L.p2v_circuit_is_self_keyed.argtypes = [vp]
+    L.p2v_verifier_resolve_keys.argtypes = [vp, u64p, sz, vp, vp, ctypes.c_uint32]
     L.p2v_circuit_from_json_gates.argtypes = [ctypes.c_char_p, sz, ctypes.c_char_p, sz, ctypes.c_uint32,
                                               ctypes.POINTER(_GateProgramC), sz, ctypes.POINTER(vp)]
     L.p2v_circuit_from_words_gates.argtypes = [u64p, sz, ctypes.c_uint32, ctypes.POINTER(_GateProgramC), sz, ctypes.POINTER(vp)]
@@ -490,6 +496,39 @@ class VerifierCircuitData:
         _check(lib().p2v_circuit_with_keys(self._h, w.ctypes.data if rows else None, len(rows), ctypes.byref(h)))
         return VerifierCircuitData(h.value)
 
+    def self_keyed(self) -> "VerifierCircuitData":
+        """This circuit marked self-keyed (p2v_circuit_self_keyed, include/p2v.h "self-keyed
+        circuits"): every entry point that takes no key ids resolves each proof's key on the
+        device from the tail of its public inputs, plonky2's add_verifier_data_public_inputs
+        convention (not the reference's); a tail that names no key of the table: ERR_CIRCUIT.
+        Explicit key_ids override the resolution.  with_keys and shape_variant keep the mark."""
+        h = ctypes.c_void_p()
+        _check(lib().p2v_circuit_self_keyed(self._h, ctypes.byref(h)))
+        return VerifierCircuitData(h.value)
+
+    @property
+    def is_self_keyed(self) -> bool:
+        rc = lib().p2v_circuit_is_self_keyed(self._h)
+        if rc < 0:
+            _check(rc)
+        return bool(rc)
+
+    def find_key(self, key_words) -> int:
+        """The lowest index of the key equal to key_words (key encoding, reduced mod p) in the
+        table (p2v_circuit_find_key), or -1."""
+        w = np.ascontiguousarray(key_words, dtype=np.uint64).reshape(-1)
+        if w.size != self.key_words:
+            raise P2VError(E_ARG, f"a key has {w.size} words, the circuit's keys have {self.key_words}")
+        return int(lib().p2v_circuit_find_key(self._h, w.ctypes.data))
+
+    def key_from_public_inputs(self, pis) -> np.ndarray:
+        """The verifier key a proof's public inputs end with, [circuit_digest | cap], in the key
+        encoding (p2v_key_from_public_inputs); P2VError(E_SHAPE) when they are shorter than a key."""
+        p = np.ascontiguousarray(pis, dtype=np.uint64).reshape(-1)
+        out = np.empty(self.key_words, dtype=np.uint64)
+        _check(lib().p2v_key_from_public_inputs(self._h, p.ctypes.data, p.size, out.ctypes.data))
+        return out
+
     def for_proof(self, proof_json: Union[str, bytes]) -> "VerifierCircuitData":
         """The circuit (or its shape variant) whose layout holds this proof's public inputs and
         final polynomial as given (the reference reads both at any length)."""
@@ -619,6 +658,18 @@ class BatchVerifier:
                                             res.ctypes.data, tr.ctypes.data if trace else None,
                                             ctypes.c_void_p(stream) if stream else None, flags))
         return (res, tr) if trace else res
+
+    def resolve_keys(self, proofs: np.ndarray, tiled: bool = False, stream: int = 0) -> np.ndarray:
+        """uint32 [n]: for each proof of the host array [n, proof_words] the index of the key its
+        public inputs end with, KEY_NONE where they name none (p2v_verifier_resolve_keys: the
+        resolution of a self-keyed run alone, on the device; any circuit, marked or not)."""
+        proofs = np.ascontiguousarray(proofs, dtype=np.uint64)
+        n = proofs.shape[0]
+        src = tile_proofs(proofs) if tiled else proofs
+        ids = np.empty(n, dtype=np.uint32)
+        _check(lib().p2v_verifier_resolve_keys(self._h, src.ctypes.data, n, ids.ctypes.data,
+                                               ctypes.c_void_p(stream) if stream else None, FLAG_INPUT_TILED if tiled else 0))
+        return ids
 
     @staticmethod
     def _json_batch(proofs):
