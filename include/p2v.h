@@ -592,6 +592,11 @@ int  p2v_verify_batch_devices(const p2v_circuit* c, const uint64_t* proofs, size
  *          -> 2 words per constraint (re, im), in commit order
  * Test hook for the parity suite (edge values the synthetic proofs never produce). */
 int  p2v_selftest(int device, int op, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n);
+/* The sizes p2v_selftest takes for `op`, from the table it runs by (host only, no device): words per
+ * item of a and of out, and the words read at b (per item for ops 0, 3, 6; 0: b is not read).  b: the
+ * nb words the caller holds, read no further; only ops 17-21 look at them, and shared words that
+ * p2v_selftest would refuse (b NULL or too short among them), a bad op and op 11 are P2V_E_ARG. */
+int  p2v_selftest_layout(int op, const uint64_t* b, size_t nb, size_t* item_words, size_t* out_words, size_t* b_words);
 
 /* Measurement helpers (bench.py; device pointers, enqueued on `stream`, no host sync):
  * p2v_count_mismatches: counters[0] += #{i < n : results[i] != expect[i]}, counters[1] += 1 --

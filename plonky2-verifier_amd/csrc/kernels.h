@@ -18,8 +18,10 @@ extern "C" __global__ void k_phase1_lane_keyed(DevCircuit, int, int);
 extern "C" __global__ void k_transcript_keyed(DevCircuit, int);
 extern "C" __global__ void k_transcript_lane_keyed(DevCircuit, int);
 extern "C" __global__ void k_leaf(DevCircuit);
+// fri.hip
 extern "C" __global__ void k_fri(DevCircuit);
 extern "C" __global__ void k_status(DevCircuit, int8_t*, uint64_t*, int64_t);
+// selftest.hip
 extern "C" __global__ void k_selftest(int, const uint64_t*, const uint64_t*, uint64_t*, int64_t);
 extern "C" __global__ void k_selftest_forms(int, const uint64_t*, uint64_t*, int64_t);
 extern "C" __global__ void k_selftest_field(int, DevCircuit, const uint64_t*, uint64_t*);
@@ -43,6 +45,8 @@ extern "C" __global__ void k_vanish_lookup_r2(DevCircuit);
 extern "C" __global__ void k_vanish_lookup_rn(DevCircuit);
 extern "C" __global__ void k_vanish_prog_r2(DevCircuit);
 extern "C" __global__ void k_vanish_prog_rn(DevCircuit);
+// (the fourth self-test kernel stays in vanish_prog.hip, not selftest.hip: the interpreter it runs
+// is file-local there on purpose, and a header for one 12-line kernel would be more machinery)
 extern "C" __global__ void k_selftest_prog(DevCircuit, uint64_t*, int);
 extern "C" __global__ void k_lut(DevCircuit);
 extern "C" __global__ void k_vanish_final(DevCircuit);

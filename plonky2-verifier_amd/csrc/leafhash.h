@@ -1,6 +1,6 @@
-// leafhash.h — what kernels.hip (phase 1, self-tests) and merkle.hip (the Merkle path kernels)
-// both need: the leaf sponge, and the LDS constant tables of the transcript forms that the row
-// form of the permutation runs on.
+// leafhash.h — what kernels.hip (phase 1), merkle.hip (the Merkle path kernels) and selftest.hip
+// need in common: the leaf sponge, and the LDS constant tables of the transcript forms that the
+// row form of the permutation runs on.
 #pragma once
 #include "devcommon.h"
 #include "qposeidon.h"

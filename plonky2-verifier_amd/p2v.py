@@ -885,40 +885,28 @@ def _status_to_bool(st: int) -> bool:
 
 
 def device_selftest(op: int, a: np.ndarray, b: Optional[np.ndarray] = None, device: int = 0) -> np.ndarray:
-    """p2v_selftest (include/p2v.h): the device field multiply (op 0, a * b mod p; op 3 the S-box's
-    form), Poseidon permutation (op 1, a = [n, 12] states), 2-to-1 compression form (op 2, words
-    8..11 taken as 0, words 0..3 returned), one MDS layer (op 4), the S-box forms (ops 5-8, x^7;
-    op 6 the grouped pair (a[i], b[i]) -> out [n, 2]) and the latency forms of the permutation
-    (ops 9-10: row, quad) on `device`.  Ops 12-20: the F / F^2 arithmetic and the FRI query
-    code (a = [n, item words], b = the op's shared words, out = [n, result words]; see p2v.h).
-    Op 21: the gate-program interpreter, b = [nwires, nconsts] + GateProgram.words().
-    Op 22: the throughput permutation's leading merged unit (a = [n, 12] S-box outputs of round 3,
-    out = the state entering round 6, canonical)."""
+    """p2v_selftest on `device`: the ops, their items and their shared words b are specified in
+    include/p2v.h.  a = n items ([n] or [n, item words]); the result is [n, out words], for the
+    hash and S-box ops (0-10, 22) of a's shape where an item gives as many words as it has.  The
+    sizes are p2v_selftest_layout's."""
     a = np.ascontiguousarray(a, dtype=np.uint64)
     n = a.shape[0]
-    if op == 21:   # b = [nwires, nconsts, program words]; out: 2 words per COMMIT of the program
-        bb = np.ascontiguousarray(b, dtype=np.uint64).reshape(-1)
-        if bb.size < 4:
+    bb = np.ascontiguousarray(b, dtype=np.uint64).reshape(-1) if b is not None else None
+    if op == 21:
+        if bb is None or bb.size < 4:
             raise ValueError("selftest op 21: b = [nwires, nconsts] + program words")
-        # p2v_selftest has no length for b and reads the encoding as far as its instruction count
-        # says; the library's own decoder, given the length, says first that the words end there
-        ncommit = gate_program_info(bb[2:])["commits"]
-        win = 2 * (int(bb[0]) + int(bb[1])) + 4
-        if a.size != n * win:
-            raise ValueError(f"selftest op 21: items of {win} words expected, got shape {a.shape}")
-        out = np.zeros((n, 2 * ncommit), dtype=np.uint64)
-        _check(lib().p2v_selftest(device, op, a.ctypes.data, bb.ctypes.data, out.ctypes.data, n))
-        return out
-    if 12 <= op <= 20:
-        win = {12: 2, 13: 4, 14: 1, 15: 2, 16: 4, 17: 1, 18: 2}.get(op)
-        if win is None:
-            win = int(b[0]) if op == 19 else 2 + (2 << int(b[0]))
-        if a.size != n * win:
-            raise ValueError(f"selftest op {op}: items of {win} words expected, got shape {a.shape}")
-        out = np.zeros((n, {12: 5, 14: 1, 16: 4, 17: 1}.get(op, 2)), dtype=np.uint64)
-    else:
-        out = np.zeros((n, 2), dtype=np.uint64) if op == 6 else np.zeros_like(a)   # op 4: b = [kl[12], kh[12]]
-    bb = np.ascontiguousarray(b, dtype=np.uint64) if b is not None else None
+        # the library's own decoder, given the length, says first where the program's words end
+        gate_program_info(bb[2:])
+    win, wout, wb = ctypes.c_size_t(), ctypes.c_size_t(), ctypes.c_size_t()
+    # typed here, not in lib(): P2V_LIB may name a measurement build that predates this function
+    _check(lib().p2v_selftest_layout(ctypes.c_int(op), ctypes.c_void_p(bb.ctypes.data if bb is not None else None),
+                                     ctypes.c_size_t(bb.size if bb is not None else 0),
+                                     ctypes.byref(win), ctypes.byref(wout), ctypes.byref(wb)))
+    if a.size != n * win.value:
+        raise ValueError(f"selftest op {op}: items of {win.value} words expected, got shape {a.shape}")
+    out = np.zeros((n, wout.value), dtype=np.uint64)
+    if (op < 12 or op == 22) and wout.value == win.value:
+        out = out.reshape(a.shape)
     _check(lib().p2v_selftest(device, op, a.ctypes.data, bb.ctypes.data if bb is not None else None, out.ctypes.data, n))
     return out
 

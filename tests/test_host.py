@@ -510,3 +510,92 @@ def test_retired_transcript_form_is_refused_before_any_device_call(monkeypatch):
     msg = L.p2v_last_error_message().decode()
     assert "pair" in msg and "retired" in msg and "5.7" in msg
     assert not out.value
+
+
+def _selftest_layout(L, op, b=None):
+    """p2v_selftest_layout through ctypes: (code, item words, out words, b words)."""
+    bb = None if b is None else np.array(b, dtype=np.uint64)
+    w = [ctypes.c_size_t(99) for _ in range(3)]
+    rc = L.p2v_selftest_layout(ctypes.c_int(op), ctypes.c_void_p(None if bb is None else bb.ctypes.data),
+                               ctypes.c_size_t(0 if bb is None else bb.size), *[ctypes.byref(x) for x in w])
+    return (rc,) + tuple(x.value for x in w)
+
+
+def _two_commit_program(p2v):
+    g = p2v.GateProgram()
+    g.commit(g.wire(0) * g.wire(2) - g.const(1))
+    g.commit(g.wire(1) + g.pi_hash(3))
+    return [int(x) for x in g.words()]
+
+
+def test_selftest_layout_gives_the_sizes_the_header_states():
+    """p2v_selftest_layout against include/p2v.h, op by op: words per item of a, of out, and the
+    words read at b (per item for ops 0, 3, 6).  No device is needed."""
+    p2v = p2v_module()
+    L = p2v.lib()
+    prog = _two_commit_program(p2v)
+    seg40 = [40, 5, 2, 10, 12, 20, 33, 8, 2, 8, 13, 7]   # op 19, W = 40: five segments inside the item
+    table = [
+        (0, None, (1, 1, 1)), (1, None, (12, 12, 0)), (2, None, (12, 12, 0)), (3, None, (1, 1, 1)),
+        (4, None, (12, 12, 24)), (5, None, (1, 1, 0)), (6, None, (1, 2, 1)), (7, None, (1, 1, 0)),
+        (8, None, (1, 1, 0)), (9, None, (12, 12, 0)), (10, None, (12, 12, 0)),
+        (12, None, (2, 5, 0)), (13, None, (4, 2, 0)), (14, None, (1, 1, 0)), (15, None, (2, 2, 0)),
+        (16, None, (4, 4, 0)), (17, [32], (1, 1, 1)), (18, [(1 << 32) - 1], (2, 2, 1)),
+        (19, [2] + [0] * 11, (2, 2, 12)), (19, seg40, (40, 2, 12)),
+        (20, [1], (6, 2, 1)), (20, [8], (514, 2, 1)),
+        (21, [3, 2] + prog, (2 * (3 + 2) + 4, 2 * 2, 2 + len(prog))),
+        (22, None, (12, 12, 0)),
+    ]
+    assert sorted({op for op, _, _ in table}) == [op for op in range(23) if op != 11]
+    for op, b, want in table:
+        assert _selftest_layout(L, op, b) == (p2v.E_OK,) + want, (op, b)
+    # words past the ones an op reads change nothing, and ops without shared words ignore b
+    assert _selftest_layout(L, 21, [3, 2] + prog + [7, 7, 7]) == (p2v.E_OK, 14, 4, 2 + len(prog))
+    assert _selftest_layout(L, 1, [5]) == (p2v.E_OK, 12, 12, 0)
+
+
+def test_selftest_layout_refuses_what_selftest_refuses():
+    """A bad op, the retired op 11 and shared words outside an op's bounds are P2V_E_ARG with a
+    message; so is a b that is NULL or ends before the words the op reads."""
+    p2v = p2v_module()
+    L = p2v.lib()
+    prog = _two_commit_program(p2v)
+    bad_magic = [3, 2] + [prog[0] ^ 1] + prog[1:]
+    refused = [
+        (-1, None), (11, None), (23, None),
+        (17, [33]), (18, [1 << 32]),
+        (19, [8, 1, 4, 0, 0, 0, 0, 5, 0, 0, 0, 0]),   # segment 0: words 4..8 of an 8-word item
+        (19, [1] + [0] * 11), (19, [8, 6] + [0] * 10),
+        (20, [0]), (20, [9]),
+        (21, bad_magic), (21, [1, 2] + prog), (21, ([3, 2] + prog)[:-1]), (21, [3, 2, prog[0]]),
+        (17, None), (18, []), (19, [2] + [0] * 10), (20, None), (21, None),
+    ]
+    for op, b in refused:
+        assert _selftest_layout(L, op, b)[0] == p2v.E_ARG, (op, b)
+        assert L.p2v_last_error_message(), (op, b)
+    assert L.p2v_selftest_layout(ctypes.c_int(1), None, ctypes.c_size_t(0), None, None, None) == p2v.E_ARG
+
+
+def test_selftest_refusals_keep_their_order():
+    """p2v_selftest: a bad op, op 11, a null argument and op 21's program checks are P2V_E_ARG before
+    any device is looked for; the shared words of ops 17-20 are checked behind the device count,
+    so without a device they are P2V_E_NODEVICE."""
+    p2v = p2v_module()
+    L = p2v.lib()
+    buf = np.zeros(64, np.uint64)
+    b = buf.ctypes.data
+    prog = _two_commit_program(p2v)
+    bad = np.array([3, 2] + [prog[0] ^ 1] + prog[1:], dtype=np.uint64)
+    for rc in (L.p2v_selftest(0, -1, b, b, b, 1), L.p2v_selftest(0, 23, b, b, b, 1), L.p2v_selftest(0, 11, b, b, b, 1),
+               L.p2v_selftest(0, 1, None, b, b, 1), L.p2v_selftest(0, 1, b, b, None, 1), L.p2v_selftest(0, 0, b, None, b, 1),
+               L.p2v_selftest(0, 4, b, None, b, 1), L.p2v_selftest(0, 6, b, None, b, 1),
+               L.p2v_selftest(0, 21, b, None, b, 0), L.p2v_selftest(0, 21, b, bad.ctypes.data, b, 1)):
+        assert rc == p2v.E_ARG
+        assert L.p2v_last_error_message()
+    if p2v.device_count() == 0:
+        bad17 = np.array([33], dtype=np.uint64)
+        good21 = np.array([3, 2] + prog, dtype=np.uint64)
+        for rc in (L.p2v_selftest(0, 1, None, None, None, 0), L.p2v_selftest(0, 5, b, None, b, 1),
+                   L.p2v_selftest(0, 17, b, bad17.ctypes.data, b, 1), L.p2v_selftest(0, 17, b, None, b, 1),
+                   L.p2v_selftest(0, 21, b, good21.ctypes.data, b, 1)):
+            assert rc == p2v.E_NODEVICE

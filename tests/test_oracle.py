@@ -214,7 +214,7 @@ def test_first_round_wrap_states_hit_their_targets():
 
 
 def test_chunked_reduce_powers_algebra():
-    """k_fri's combineInitial (round 5, kernels.hip reduce_powers): Horner in chunks of 8,
+    """k_fri's combineInitial (round 5, fri.h reduce_powers): Horner in chunks of 8,
     g <- g a^8 + sum_{k<8} y_{j+k} a^k, whose inner sums of base-field products are kept as
     lo + hi 2^64 + top 2^128 and reduced with 2^128 == -2^32 (mod p), equals the reference's
     reduceWithPowers sum_i a^i y_i (Goldilocks.hs:180-183) in F^2 = F[X]/(X^2 - 7), for list

@@ -381,7 +381,7 @@ def test_literal_fri_query_values_match_oracle_trace(idx):
 
 
 def test_fold16_in_halves_is_the_same_interpolant():
-    """k_fri folds an arity-16 coset in two halves (kernels.hip fold16_halves):
+    """k_fri folds an arity-16 coset in two halves (fri.h fold16_halves):
     with v the coset values in received order (vals[rev k] = v[k]), E / O the 8-point transforms
     of v[0..7] / v[8..15] and w = omega_16, sum_k c_k b^k = (1 + b^8) E(b) + (1 - b^8) O(w^-1 b),
     where c_k = sum_j vals_j w^(-jk).  Exact integers, against that direct sum."""

@@ -12,7 +12,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "plonky2-verifier_amd")
-FILES = ["kernels", "merkle", "vanish", "vanish_poseidon", "vanish_prog", "json_pack", "keys"]
+FILES = ["kernels", "fri", "selftest", "merkle", "vanish", "vanish_poseidon", "vanish_prog", "json_pack", "keys"]
 
 
 def usage(name, extra):
