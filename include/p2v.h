@@ -556,7 +556,19 @@ int  p2v_verify_batch_devices(const p2v_circuit* c, const uint64_t* proofs, size
  *   op 22: out[12i..] = the leading merged unit of the throughput permutation on u = a[12i..], the
  *         S-box outputs of full round 3: that round's MDS and partial rounds 4-5 as one unit, i.e.
  *         the state entering round 6, canonical (Poseidon.hs:48-60)
- * Inputs of ops 0-10 and 22 may be any u64 (values >= p are congruent, as the reference reads them).
+ *   op 23: out[12i..] = the Poseidon permutation of a[12i..] through one of the template instances
+ *         of the throughput form that the verifier kernels run.  b = 3 shared words: form (0 the
+ *         leaf sponge's and the transcript's, 1 the Merkle path kernel's, with its own partial-round
+ *         schedule, 2 the lane transcript's), zh (0 or 1; 1: words 8..11 of a[12i..] are taken as
+ *         0 and round 0 runs in its peeled form), gm (1..7; bit k = output words 4k..4k+3 are
+ *         formed and canonical; the other words are returned as 0)   (Hash/Poseidon.hs:42-46)
+ *   op 24: out[4i..] = the leaf sponge's digest of the item's len words (overwrite mode, no
+ *         padding: Hash/Sponge.hs:26-31).  b = 2 shared words: len <= 2^20 (0: the zero digest),
+ *         noop_leaves (0 or 1; 1 with len <= 4: the zero-padded leaf is its own digest, the
+ *         P2V_EXT_HASH_OR_NOOP convention, and its words are canonical).  len words -> 4
+ * Inputs of ops 0-10 and 22-24 may be any u64 (values >= p are congruent, as the reference reads
+ * them) except where stated.  Ops 23-24 read their items as ops 12-20 do, and refuse shared words
+ * outside the stated ranges with P2V_E_ARG.
  *
  * Ops 12-20: the F / F^2 arithmetic and the FRI query code of k_fri and the vanishing kernels,
  * each op the production function itself, one lane per item; a = n items of the stated words,
@@ -594,7 +606,7 @@ int  p2v_verify_batch_devices(const p2v_circuit* c, const uint64_t* proofs, size
 int  p2v_selftest(int device, int op, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n);
 /* The sizes p2v_selftest takes for `op`, from the table it runs by (host only, no device): words per
  * item of a and of out, and the words read at b (per item for ops 0, 3, 6; 0: b is not read).  b: the
- * nb words the caller holds, read no further; only ops 17-21 look at them, and shared words that
+ * nb words the caller holds, read no further; only ops 17-21 and 23-24 look at them, and shared words that
  * p2v_selftest would refuse (b NULL or too short among them), a bad op and op 11 are P2V_E_ARG. */
 int  p2v_selftest_layout(int op, const uint64_t* b, size_t nb, size_t* item_words, size_t* out_words, size_t* b_words);
 

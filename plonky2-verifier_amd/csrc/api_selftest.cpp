@@ -61,7 +61,22 @@ static int shared_prog(const uint64_t* b, size_t nb, OpLayout& L) {
   return P2V_OK;
 }
 
-enum Family : uint8_t { K_SELFTEST, K_FORMS, K_FIELD, K_PROG, RETIRED };
+// op 23: b = form, zh, gm: the template instance of permute_dev and its two uniform arguments
+static int shared_perm_variant(const uint64_t* b, size_t nb, OpLayout&) {
+  if (!b || nb < 3) return bad_b();
+  if (b[0] > 2 || b[1] > 1 || b[2] < 1 || b[2] > 7) return fail(P2V_E_ARG, "permutation variant: form > 2, zh > 1 or gm outside 1..7");
+  return P2V_OK;
+}
+// op 24: b = len, noop_leaves; the item is the leaf's len words
+static int shared_leaf_sponge(const uint64_t* b, size_t nb, OpLayout& L) {
+  if (!b || nb < 2) return bad_b();
+  if (b[0] > (1u << 20) || b[1] > 1) return fail(P2V_E_ARG, "leaf_sponge: len > 2^20 or noop_leaves > 1");
+  L.in = (size_t)b[0];
+  return P2V_OK;
+}
+
+// K_HASH runs as K_FIELD does (its items read as a proof batch), in k_selftest_hash
+enum Family : uint8_t { K_SELFTEST, K_FORMS, K_FIELD, K_HASH, K_PROG, RETIRED };
 enum BKind : uint8_t { B_NONE, B_ITEM, B_SHARED };   // b: absent, b[i] beside a[i], or one block for all items
 struct SelftestOp {
   Family kernel;
@@ -73,7 +88,7 @@ struct SelftestOp {
                       // ops 12-20 behind hipSetDevice, op 21 ahead of the device count)
   SharedCheck check;  // of the shared words; ops without one only need b non-null
 };
-static const SelftestOp kOps[23] = {
+static const SelftestOp kOps[25] = {
     /*  0 gl::mul            */ {K_SELFTEST, 1, 1, 1, B_ITEM, 1, true, nullptr},
     /*  1 permutation        */ {K_SELFTEST, 12, 12, 0, B_NONE, 1, true, nullptr},
     /*  2 compression        */ {K_SELFTEST, 12, 12, 0, B_NONE, 1, true, nullptr},
@@ -98,9 +113,11 @@ static const SelftestOp kOps[23] = {
     /* 20 fold_step          */ {K_FIELD, 0, 2, 1, B_SHARED, 1, false, shared_fold},
     /* 21 gate program       */ {K_PROG, 0, 0, 0, B_SHARED, 1, false, shared_prog},
     /* 22 leading merged unit*/ {K_FORMS, 12, 12, 0, B_NONE, 1, true, nullptr},
+    /* 23 permutation variant*/ {K_HASH, 12, 12, 3, B_SHARED, 1, false, shared_perm_variant},
+    /* 24 leaf_sponge        */ {K_HASH, 0, 4, 2, B_SHARED, 1, false, shared_leaf_sponge},
 };
 static const SelftestOp* selftest_op(int op) {
-  return op < 0 || op > 22 || kOps[op].kernel == RETIRED ? nullptr : &kOps[op];
+  return op < 0 || op > 24 || kOps[op].kernel == RETIRED ? nullptr : &kOps[op];
 }
 // the row's sizes, then what the op's check makes of b
 static int selftest_layout(const SelftestOp& R, const uint64_t* b, size_t nb, OpLayout& L) {
@@ -134,7 +151,8 @@ extern "C" {
 
 // p2v_selftest ops 12-20: the field and FRI query code on items read as a proof batch is, through
 // a DevCircuit that holds the item array and the tables fill_scalars / fri_twiddles make for a
-// circuit with FRI arity bits 1..8 (step s = ab - 1).
+// circuit with FRI arity bits 1..8 (step s = ab - 1).  Ops 23-24 (K_HASH) read their items the same
+// way; op 24's noop_leaves travels in the DevCircuit, where leaf_sponge looks for it.
 static int selftest_field(const SelftestOp& R, int op, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n) {
   OpLayout L;
   RCK(selftest_layout(R, b, SIZE_MAX, L));
@@ -145,11 +163,14 @@ static int selftest_field(const SelftestOp& R, int op, const uint64_t* a, const 
   C.step_depth.assign(8, 0); C.L.step_evals.assign(8, 0); C.L.step_path.assign(8, 0);
   DevCircuit d{};
   fill_scalars(C, d);
+  if (op == 24) d.noop_leaves = (int32_t)b[1];
   DevBuf dtw;
   return selftest_on_device(R, L, a, b, out, n, [&](const uint64_t* da, const uint64_t* db, uint64_t* dout) {
     SCK(upload(dtw, fri_twiddles(C), d.twiddles));
     items_as_batch(d, da, L.in, n);
-    hipLaunchKernelGGL(k_selftest_field, dim3((unsigned)((n * R.lanes + 255) / 256)), dim3(256), 0, 0, op, d, db, dout);
+    const dim3 grid((unsigned)((n * R.lanes + 255) / 256));
+    if (R.kernel == K_HASH) hipLaunchKernelGGL(k_selftest_hash, grid, dim3(256), 0, 0, op, d, db, dout);
+    else hipLaunchKernelGGL(k_selftest_field, grid, dim3(256), 0, 0, op, d, db, dout);
     return P2V_OK;
   });
 }
@@ -188,7 +209,7 @@ int p2v_selftest(int device, int op, const uint64_t* a, const uint64_t* b, uint6
   if (device < 0 || device >= ndev) return fail(P2V_E_ARG, "bad device index");
   if (R->empty_first && n == 0) return P2V_OK;
   HCK(hipSetDevice(device));
-  if (R->kernel == K_FIELD) return selftest_field(*R, op, a, b, out, n);
+  if (R->kernel == K_FIELD || R->kernel == K_HASH) return selftest_field(*R, op, a, b, out, n);
   OpLayout L;
   RCK(selftest_layout(*R, b, SIZE_MAX, L));
   const dim3 grid((unsigned)((n * R->lanes + 255) / 256));

@@ -24,6 +24,7 @@ extern "C" __global__ void k_status(DevCircuit, int8_t*, uint64_t*, int64_t);
 // selftest.hip
 extern "C" __global__ void k_selftest(int, const uint64_t*, const uint64_t*, uint64_t*, int64_t);
 extern "C" __global__ void k_selftest_forms(int, const uint64_t*, uint64_t*, int64_t);
+extern "C" __global__ void k_selftest_hash(int, DevCircuit, const uint64_t*, uint64_t*);
 extern "C" __global__ void k_selftest_field(int, DevCircuit, const uint64_t*, uint64_t*);
 // merkle.hip
 extern "C" __global__ void k_merkle(DevCircuit);

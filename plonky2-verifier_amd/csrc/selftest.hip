@@ -77,8 +77,9 @@ extern "C" __global__ void __launch_bounds__(256) k_selftest(int op, const uint6
 // n - 1 and store nothing.  a, out: n states of 12 words.
 // Op 22: the leading merged unit of the throughput form alone (poseidon.h PFTab, dv::pblock<3, true>),
 // one lane per item: a = the 12 S-box outputs u of full round 3 (any u64), out = the state entering
-// round 6, canonical.  u cannot be steered through a whole permutation, so the unit's row
-// reductions and their rare carry fix-ups are driven here.
+// round 6, canonical.  The unit's row reductions and their rare carry fix-ups are driven here on u
+// itself; inside a whole permutation u is steered by running the rounds before it backwards (every
+// round is invertible: tests/poseidon_steer.py), which is how op 23 reaches them.
 extern "C" __global__ void __launch_bounds__(256) k_selftest_forms(int op, const uint64_t* a, uint64_t* out, int64_t n) {
   if (op == 22) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -110,6 +111,42 @@ extern "C" __global__ void __launch_bounds__(256) k_selftest_forms(int op, const
     uint64_t x[3] = {s[3 * t], s[3 * t + 1], s[3 * t + 2]};
     qp::permute(x, t, T.q);
     if (item < n) for (int k = 0; k < 3; k++) o[3 * t + k] = x[k];
+  }
+}
+
+// The template instances of the throughput permutation that production runs, and the leaf sponge
+// that picks among them (p2v_selftest ops 23-24, include/p2v.h), in a kernel of their own so that
+// k_selftest keeps its registers.  One lane per item; the items are read as a proof batch is
+// (k_selftest_field below), so lanes past n re-read item n - 1 and store nothing.
+// Op 23: b = form, zh, gm.  form 0 permute_dev<true, true> (the leaf sponge, the transcript's
+// throughput form), 1 permute_dev<true, false> (k_merkle: PM_SCHED's blocks, pblock<2>), 2
+// permute_dev<false, true> (the lane transcript).  zh: words 8..11 are taken as 0.  Output groups
+// outside gm are returned as 0: the device leaves them undefined.
+// Op 24: b = len, noop_leaves (the latter arrives as c.noop_leaves): leaf_sponge over the item's len
+// words, out = the 4 digest words.
+extern "C" __global__ void __launch_bounds__(256) k_selftest_hash(int op, DevCircuit c, const uint64_t* b, uint64_t* out) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int p = (int)i;
+  const bool live = i < c.n;
+  uint64_t s[12];
+  if (op == 23) {
+    const int form = (int)b[0], gm = (int)b[2];
+    const bool zh = b[1] != 0;
+#pragma unroll
+    for (int k = 0; k < 12; k++) s[k] = zh && k >= 8 ? 0 : ld(c, k, p);
+    if (form == 0) p2::permute_dev<true, true>(s, zh, gm);
+    else if (form == 1) p2::permute_dev<true, false>(s, zh, gm);
+    else p2::permute_dev<false, true>(s, zh, gm);
+    if (live) {
+#pragma unroll
+      for (int k = 0; k < 12; k++) out[12 * i + k] = (gm >> (k >> 2)) & 1 ? s[k] : 0;
+    }
+  } else {
+    leaf_sponge(c, 0, (int)b[0], p, s);
+    if (live) {
+#pragma unroll
+      for (int k = 0; k < 4; k++) out[4 * i + k] = s[k];
+    }
   }
 }
 

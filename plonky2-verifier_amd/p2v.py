@@ -888,7 +888,7 @@ def device_selftest(op: int, a: np.ndarray, b: Optional[np.ndarray] = None, devi
     """p2v_selftest on `device`: the ops, their items and their shared words b are specified in
     include/p2v.h.  a = n items ([n] or [n, item words]); the result is [n, out words], for the
     hash and S-box ops (0-10, 22) of a's shape where an item gives as many words as it has.  The
-    sizes are p2v_selftest_layout's."""
+    sizes are p2v_selftest_layout's (op 24 with len 0: a = [n, 0])."""
     a = np.ascontiguousarray(a, dtype=np.uint64)
     n = a.shape[0]
     bb = np.ascontiguousarray(b, dtype=np.uint64).reshape(-1) if b is not None else None

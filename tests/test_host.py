@@ -545,8 +545,10 @@ def test_selftest_layout_gives_the_sizes_the_header_states():
         (20, [1], (6, 2, 1)), (20, [8], (514, 2, 1)),
         (21, [3, 2] + prog, (2 * (3 + 2) + 4, 2 * 2, 2 + len(prog))),
         (22, None, (12, 12, 0)),
+        (23, [0, 0, 7], (12, 12, 3)), (23, [2, 1, 1], (12, 12, 3)),
+        (24, [0, 0], (0, 4, 2)), (24, [135, 1], (135, 4, 2)), (24, [1 << 20, 0], (1 << 20, 4, 2)),
     ]
-    assert sorted({op for op, _, _ in table}) == [op for op in range(23) if op != 11]
+    assert sorted({op for op, _, _ in table}) == [op for op in range(25) if op != 11]
     for op, b, want in table:
         assert _selftest_layout(L, op, b) == (p2v.E_OK,) + want, (op, b)
     # words past the ones an op reads change nothing, and ops without shared words ignore b
@@ -562,8 +564,10 @@ def test_selftest_layout_refuses_what_selftest_refuses():
     prog = _two_commit_program(p2v)
     bad_magic = [3, 2] + [prog[0] ^ 1] + prog[1:]
     refused = [
-        (-1, None), (11, None), (23, None),
+        (-1, None), (11, None), (25, None),
         (17, [33]), (18, [1 << 32]),
+        (23, [3, 0, 7]), (23, [0, 2, 7]), (23, [0, 0, 0]), (23, [0, 0, 8]), (23, [0, 1]), (23, None),
+        (24, [(1 << 20) + 1, 0]), (24, [8, 2]), (24, [8]), (24, None),
         (19, [8, 1, 4, 0, 0, 0, 0, 5, 0, 0, 0, 0]),   # segment 0: words 4..8 of an 8-word item
         (19, [1] + [0] * 11), (19, [8, 6] + [0] * 10),
         (20, [0]), (20, [9]),
@@ -579,14 +583,14 @@ def test_selftest_layout_refuses_what_selftest_refuses():
 def test_selftest_refusals_keep_their_order():
     """p2v_selftest: a bad op, op 11, a null argument and op 21's program checks are P2V_E_ARG before
     any device is looked for; the shared words of ops 17-20 are checked behind the device count,
-    so without a device they are P2V_E_NODEVICE."""
+    and those of ops 23-24 with them, so without a device they are P2V_E_NODEVICE."""
     p2v = p2v_module()
     L = p2v.lib()
     buf = np.zeros(64, np.uint64)
     b = buf.ctypes.data
     prog = _two_commit_program(p2v)
     bad = np.array([3, 2] + [prog[0] ^ 1] + prog[1:], dtype=np.uint64)
-    for rc in (L.p2v_selftest(0, -1, b, b, b, 1), L.p2v_selftest(0, 23, b, b, b, 1), L.p2v_selftest(0, 11, b, b, b, 1),
+    for rc in (L.p2v_selftest(0, -1, b, b, b, 1), L.p2v_selftest(0, 25, b, b, b, 1), L.p2v_selftest(0, 11, b, b, b, 1),
                L.p2v_selftest(0, 1, None, b, b, 1), L.p2v_selftest(0, 1, b, b, None, 1), L.p2v_selftest(0, 0, b, None, b, 1),
                L.p2v_selftest(0, 4, b, None, b, 1), L.p2v_selftest(0, 6, b, None, b, 1),
                L.p2v_selftest(0, 21, b, None, b, 0), L.p2v_selftest(0, 21, b, bad.ctypes.data, b, 1)):
@@ -594,8 +598,10 @@ def test_selftest_refusals_keep_their_order():
         assert L.p2v_last_error_message()
     if p2v.device_count() == 0:
         bad17 = np.array([33], dtype=np.uint64)
+        bad23 = np.array([3, 0, 7], dtype=np.uint64)
         good21 = np.array([3, 2] + prog, dtype=np.uint64)
         for rc in (L.p2v_selftest(0, 1, None, None, None, 0), L.p2v_selftest(0, 5, b, None, b, 1),
                    L.p2v_selftest(0, 17, b, bad17.ctypes.data, b, 1), L.p2v_selftest(0, 17, b, None, b, 1),
+                   L.p2v_selftest(0, 23, b, bad23.ctypes.data, b, 1), L.p2v_selftest(0, 24, b, None, b, 1),
                    L.p2v_selftest(0, 21, b, good21.ctypes.data, b, 1)):
             assert rc == p2v.E_NODEVICE

@@ -49,7 +49,13 @@ int main() {
   sizes(19, &w40, 40, 2, 12);
   sizes(20, &ab1, 6, 2, 1);
   sizes(20, &ab8, 514, 2, 1);
-  for (int op : {-1, 11, 23}) refused(op, nullptr);
+  const V pv0{0, 0, 7}, pv2{2, 1, 1}, leaf0{0, 0}, leaf135{135, 1}, leafmax{1ull << 20, 0};
+  sizes(23, &pv0, 12, 12, 3);
+  sizes(23, &pv2, 12, 12, 3);
+  sizes(24, &leaf0, 0, 4, 2);
+  sizes(24, &leaf135, 135, 4, 2);
+  sizes(24, &leafmax, 1u << 20, 4, 2);
+  for (int op : {-1, 11, 25}) refused(op, nullptr);
   const V k33{33}, e2_32{1ull << 32}, past{8, 1, 4, 0, 0, 0, 0, 5, 0, 0, 0, 0}, short19{2, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, ab0{0}, ab9{9}, none{};
   refused(17, &k33);
   refused(18, &e2_32);
@@ -57,7 +63,10 @@ int main() {
   refused(19, &short19);
   refused(20, &ab0);
   refused(20, &ab9);
-  for (int op : {17, 18, 19, 20, 21}) { refused(op, nullptr); refused(op, &none); }
+  const V form3{3, 0, 7}, zh2{0, 2, 7}, gm0{0, 0, 0}, gm8{0, 0, 8}, short23{0, 1}, long24{(1ull << 20) + 1, 0}, noop2{8, 2}, short24{8};
+  for (const V* b : {&form3, &zh2, &gm0, &gm8, &short23}) refused(23, b);
+  for (const V* b : {&long24, &noop2, &short24}) refused(24, b);
+  for (int op : {17, 18, 19, 20, 21, 23, 24}) { refused(op, nullptr); refused(op, &none); }
   // op 21: nwires, nconsts, then c0 = w2 * k1, c1 = pih3 (WIRE 2, CONST 1, MUL 0 1, COMMIT 2, PIHASH 3, COMMIT 3)
   const V prog{3, 2, MAGIC, 6, 0, 2, 1, 1, 6, 0, 1, 8, 2, 2, 3, 8, 3};
   sizes(21, &prog, 2 * (3 + 2) + 4, 2 * 2, prog.size());
